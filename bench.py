@@ -1,6 +1,6 @@
 """Headline benchmark: unsupervised OGC segmentation training throughput on 8192-point KITTI-SF-shaped scenes.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -11,9 +11,12 @@ NaN-gradient check, Adam step.  Inputs are synthetic and seeded: four distinct b
 timed steps (the same steps with the host-to-device copy of every batch inside: `ms_per_step_with_h2d`).  Weak scaling: every
 rank has its own batch; gradients are averaged over RCCL by one flat ~2.4 MB all-reduce per step (utils/dist_util.py).
 
-Rank 0 prints ONE JSON line: value = whole-job point-clouds/s.  `roofline` is measured live (HIP events on the
-launch stream, inside the timed steps) for the ball-query kernel, the kernel BASELINE.json's metric names;
-`cpu_baseline` is the same step on the host cores with the CPU oracle's operators, on a bounded sample.
+Rank 0 prints ONE JSON line: value = whole-job point-clouds/s, ms_per_step = one timed step.  A plain run does nothing else;
+with --full the line also carries `roofline`, measured live (HIP events on the launch stream, inside the timed steps) for the
+ball-query kernel, the kernel BASELINE.json's metric names, the readings taken after the timed steps (graph replay, other
+configurations, operator tables), and `cpu_baseline`, the same step on the host cores with the CPU oracle's operators, on a
+bounded sample.  --dump-outputs DIR writes the losses and gradients of the timed step on the last timed step's batch, from the
+seeded initial weights (dump_outputs).
 """
 import argparse
 import json
@@ -120,11 +123,58 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=4, help="samples per GPU (config batch_size: 4)")
     ap.add_argument("--npoint", type=int, default=8192)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-launch timing of the search kernels inside the timed steps (roofline, "
+                         "kernel_ms), the extras after them (graph replay, operator tables, other configurations, copies), the "
+                         "offline block, the collective's timing and the CPU baseline.  Without it the run sets up, warms up, times "
+                         "the steps and prints the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline / cpu_ops")
     ap.add_argument("--timed-only", action="store_true",
-                    help="print the line after the timed steps: no extras (graph replay, operator tables, copies), no CPU baseline — "
-                         "what the rocprofv3 --pmc passes of tools/pmc_step.sh run")
+                    help="with --full: the timed steps' per-launch readings and the offline block, but no extras (graph replay, "
+                         "operator tables, copies) and no CPU baseline.  A plain run has none of them either (the rocprofv3 --pmc "
+                         "passes of tools/pmc_step.sh give it, for command lines written before --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more on the last timed step's batch from the seeded "
+                         "initial weights, and write what it computed as DIR/<name>.npy: its loss terms (loss_<term>, float64), "
+                         "the optimizer flag (stepped) and the parameters' gradients (grad.<name>, float32; ~2.4 MB in all).  "
+                         "Not timed")
     return ap.parse_args()
+
+
+def segnet_c4(npoint):
+    """The headline's network (segnet_kitti at config C4), initialised from the same seed in every run."""
+    from ogc_amd.models.segnet_kitti import MaskFormer3D
+    torch.manual_seed(10)  # random_seed: 10 in the reference YAMLs; identical init on every rank
+    return MaskFormer3D(n_slot=10, n_point=npoint, use_xyz=True, n_transformer_layer=2,
+                        transformer_embed_dim=128, transformer_input_pos_enc=False)
+
+
+def dump_outputs(path, a, dev, batch, it):
+    """--dump-outputs: the timed path (train_step, the same kernels) once more on the batch of the last timed step, from the
+    seeded initial weights with a fresh optimizer: the (loss_dict, stepped) pair it returns and the gradients it computed.  The
+    timed steps' own weights are not used: each step sums gradients with atomic adds, so after K steps the weights differ between
+    runs by rounding that K steps of training have amplified; from fixed inputs one step's outputs agree between runs to
+    rounding.  Nor are the updated parameters written: the gradient of the attention layers' key bias is zero in exact
+    arithmetic (softmax ignores a constant added to every logit of a row), so it is computed as rounding noise, and Adam's first
+    update (lr * g / |g|) turns the sign of that noise into a full step of lr."""
+    import numpy as np
+    from ogc_amd.train_step import KITTI_LOSS, build_criterion, make_optimizer, train_step
+    net = segnet_c4(a.npoint).to(dev)
+    opt = make_optimizer(net.parameters(), lr=1e-3, weight_decay=0.0)
+    torch.manual_seed(10)
+    loss_dict, stepped = train_step(net, build_criterion(KITTI_LOSS), opt, batch, it, True)
+    torch.cuda.synchronize()
+    arrays = {"loss_%s" % k: np.asarray(v, dtype=np.float64) for k, v in loss_dict.items()}
+    arrays["stepped"] = np.asarray(float(bool(stepped)), dtype=np.float32)
+    for name, p in net.named_parameters():
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    total = sum(x.nbytes for x in arrays.values())
+    assert total <= 64 * 2 ** 20, "outputs of %d bytes: more than the 64 MB a dump may hold" % total
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+    del net, opt
 
 
 def cpu_baseline(npoint):
@@ -531,6 +581,74 @@ def config3_flow_train_reading(dev, steps=8, warm=3):
             "loss_sum": round(float(losses["sum"]), 5)}
 
 
+def launch_readings(timer, offline, a, isolated_ms, pair_floor_ms):
+    """--full: the roofline of the ball query and the mean durations of the other search launches, from the HIP event pairs
+    LaunchTimer recorded around them inside the timed steps -> (roofline, kernel_ms)."""
+    durs = timer.durations_ms()
+    # In the step the ball query runs on the cell grid it shares with the loss's k-NN (ogc_cell_grid_build once per step for
+    # both searches, ogc_ball_query_cells / ogc_knn_clamped_cells on it): the operator's time is its query launch plus its
+    # HALF of the build.  `query_only` and the stand-alone operator (its own build + query, idle GPU) are reported next to it.
+    bq = durs.get("ogc_ball_query_cells", [])
+    shared = bool(bq)
+    if not shared:
+        bq = durs.get("ogc_ball_query", [])
+    roof = None
+    if bq:
+        ms_q = sum(d for d, _ in bq) / len(bq)
+        builds = durs.get("ogc_cell_grid_build", [])
+        ms_b = sum(d for d, _ in builds) / len(builds) if builds else 0.0
+        ms = ms_q + 0.5 * ms_b if shared else ms_q
+        dims = bq[0][1]
+        b_, n_, ns_ = (dims[0], dims[1], dims[3]) if shared else (dims[0], dims[1], dims[4])
+        m_ = n_
+        alg = b_ * (12 * m_ + 12 * n_ + 4 * m_ * ns_)            # SURVEY §8d: 12M + 12N + 4M*nsample per cloud
+        gbs = alg / (ms * 1e-3) / 1e9
+        roof = {"kernel": ("ogc_ball_query_cells (ball_query_cells_kernel<64, 1>) on the cell grid shared with the loss's k-NN, plus "
+                           "half of ogc_cell_grid_build (grid_build_split_kernel<8>)") if shared else
+                          "ogc_ball_query (grid_build_split_kernel<8> + ball_query_cells_kernel<64, 1>)",
+                "bound": "hbm", "achieved": round(gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(gbs / HBM_PEAK_GBS, 5),
+                "traffic": (offline["ball_query_traffic_bytes"]["bytes"]
+                            if [b_, n_, m_, ns_] == offline["ball_query_traffic_bytes"]["shape"] else None),
+                "traffic_source": offline["ball_query_traffic_bytes"].get("source"),
+                "launches": len(bq), "avg_ms": round(ms, 4), "algorithmic_bytes": alg,
+                "query_only": {"avg_ms": round(ms_q, 4), "achieved": round(alg / (ms_q * 1e-3) / 1e9, 2),
+                               "frac": round(alg / (ms_q * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
+                "grid_build": {"avg_ms": round(ms_b, 4), "launches_per_step": len(builds) / max(a.steps, 1),
+                               "shared_by": "ogc_knn_clamped_cells (k-NN of the smoothness term) and ogc_ball_query_cells"},
+                # per-launch event pairs read ~4.6 us with nothing between them (two marker packets): the same launches
+                # with that floor removed, which is what the kernel trace of this command shows (profiles/, DESIGN 6)
+                "event_pair_floor_ms": round(pair_floor_ms, 5),
+                "floor_removed": (lambda q, bld: {"avg_ms": round(q + 0.5 * bld, 4), "query_ms": round(q, 4), "build_ms": round(bld, 4),
+                                                  "achieved": round(alg / ((q + 0.5 * bld) * 1e-3) / 1e9, 2),
+                                                  "frac": round(alg / ((q + 0.5 * bld) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)})(
+                    max(ms_q - pair_floor_ms, 1e-6), max(ms_b - pair_floor_ms, 0.0) if shared else 0.0),
+                "isolated": None if isolated_ms is None else {
+                    "avg_ms": round(isolated_ms, 4), "achieved": round(alg / (isolated_ms * 1e-3) / 1e9, 2),
+                    "frac": round(alg / (isolated_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                    "note": "the stand-alone operator ogc_ball_query (its own grid build + query), 20 back-to-back "
+                            "launches on an idle GPU after the timed region"},
+                "shape": {"B": b_, "N": n_, "M": m_, "nsample": ns_},
+                "note": "algorithmic bytes = B*(12M + 12N + 4M*nsample) (SURVEY 8d) / mean duration (HIP events on the launch "
+                        "stream, inside the timed steps) of the query launch + half of the grid build it shares with the k-NN "
+                        "search; the exact cell-list search tests ~N/60 candidates per centre, so the all-pairs figure of "
+                        "8*B*N*M flop no longer describes the work done.  A pair of HIP events reads event_pair_floor_ms with "
+                        "NOTHING between them (measured live, idle GPU): achieved / frac / avg_ms are the raw readings, "
+                        "floor_removed the same launches with that floor taken off, which is what the rocprofv3 kernel "
+                        "statistics of this command show (profiles/rNN_bench_kernel_stats.csv of the newest round; tools/bench_ops.py has the "
+                        "idle-GPU table)",
+                "all_pairs_equivalent_tpairs_per_s": round(b_ * n_ * m_ / (ms * 1e-3) / 1e12, 2)}
+    others = {}
+    for name in ("ogc_knn_clamped", "ogc_knn_clamped_cells", "ogc_cell_grid_build", "ogc_furthest_point_sampling",
+                 "ogc_furthest_point_sampling_chain"):
+        if name in durs:
+            per = {}
+            for d, dims in durs[name]:
+                per.setdefault(str(dims[:4]), []).append(d)
+            others[name] = {k: round(sum(v) / len(v), 4) for k, v in per.items()}
+    return roof, others
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -563,9 +681,7 @@ def main():
     KITTI_K = KITTI_LOSS["smooth_loss_params"]["knn_loss_params"]["k"]
     KITTI_R = KITTI_LOSS["smooth_loss_params"]["knn_loss_params"]["radius"]
 
-    torch.manual_seed(10)  # random_seed: 10 in the reference YAMLs; identical init on every rank
-    net = MaskFormer3D(n_slot=10, n_point=a.npoint, use_xyz=True, n_transformer_layer=2,
-                       transformer_embed_dim=128, transformer_input_pos_enc=False).to(dev)
+    net = segnet_c4(a.npoint).to(dev)
     model = net
     if dist.is_initialized():
         # one flat gradient all-reduce per step instead of DistributedDataParallel's per-parameter hooks (its host
@@ -603,12 +719,14 @@ def main():
                          next_batch=batches[(step_no + 1) % NB]).prefetched
         step_no += 1
     sync()
-    if hasattr(model, "time_collectives"):
+    if a.full and hasattr(model, "time_collectives"):
         model.time_collectives(True)
     timed_ops = {"ogc_ball_query", "ogc_ball_query_cells", "ogc_cell_grid_build", "ogc_knn_clamped_cells", "ogc_knn_clamped",
                  "ogc_furthest_point_sampling", "ogc_furthest_point_sampling_chain"}
-    # (the event pairs of these ~12 launches per step cost the step < 0.05 ms: measured with the roofline's three alone)
-    with nat.LaunchTimer(timed_ops) as timer:
+    # (the event pairs of these ~12 launches per step cost the step < 0.05 ms: measured with the roofline's three alone;
+    # a plain run records none)
+    import contextlib
+    with (nat.LaunchTimer(timed_ops) if a.full else contextlib.nullcontext()) as timer:
         t0 = time.perf_counter()
         mark = bool(os.environ.get("OGC_BENCH_MARK"))  # profiling aid: a marker kernel per step (tools/prof_summary.py)
         for _ in range(a.steps):
@@ -631,13 +749,16 @@ def main():
     if dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    peak_hbm = torch.cuda.max_memory_allocated()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, a, dev, batches[(step_no - 1) % NB], it)
 
     isolated_ms, extras, pair_floor_ms = None, {}, 0.0
     if a.timed_only:
         a.no_cpu_baseline = True
     # The extras are single-GPU readings taken by rank 0 alone after the timed region; some of them run further training steps,
     # i.e. gradient collectives the other ranks would not join: with more than one rank the line carries the timed region only.
-    if rank == 0 and not a.timed_only and world == 1:
+    if a.full and rank == 0 and not a.timed_only and world == 1:
         def graph_reading():
             # the same step replayed as ONE HIP graph (ogc_amd/graph_step.py; `--hip-graph` of the training driver): what a step
             # costs when the launch thread is out of the picture.  A second network / optimizer (the capture needs step counts
@@ -735,69 +856,6 @@ def main():
             graph_reading()
         extras.update(graph_extras)
     if rank == 0:
-        offline = load_offline()
-        durs = timer.durations_ms()
-        # In the step the ball query runs on the cell grid it shares with the loss's k-NN (ogc_cell_grid_build once per step for
-        # both searches, ogc_ball_query_cells / ogc_knn_clamped_cells on it): the operator's time is its query launch plus its
-        # HALF of the build.  `query_only` and the stand-alone operator (its own build + query, idle GPU) are reported next to it.
-        bq = durs.get("ogc_ball_query_cells", [])
-        shared = bool(bq)
-        if not shared:
-            bq = durs.get("ogc_ball_query", [])
-        roof = None
-        if bq:
-            ms_q = sum(d for d, _ in bq) / len(bq)
-            builds = durs.get("ogc_cell_grid_build", [])
-            ms_b = sum(d for d, _ in builds) / len(builds) if builds else 0.0
-            ms = ms_q + 0.5 * ms_b if shared else ms_q
-            dims = bq[0][1]
-            b_, n_, ns_ = (dims[0], dims[1], dims[3]) if shared else (dims[0], dims[1], dims[4])
-            m_ = n_
-            alg = b_ * (12 * m_ + 12 * n_ + 4 * m_ * ns_)            # 12M + 12N + 4M*nsample per cloud
-            gbs = alg / (ms * 1e-3) / 1e9
-            roof = {"kernel": ("ogc_ball_query_cells (ball_query_cells_kernel<64, 1>) on the cell grid shared with the loss's k-NN, plus "
-                               "half of ogc_cell_grid_build (grid_build_split_kernel<8>)") if shared else
-                              "ogc_ball_query (grid_build_split_kernel<8> + ball_query_cells_kernel<64, 1>)",
-                    "bound": "hbm", "achieved": round(gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(gbs / HBM_PEAK_GBS, 5),
-                    "traffic": (offline["ball_query_traffic_bytes"]["bytes"]
-                                if [b_, n_, m_, ns_] == offline["ball_query_traffic_bytes"]["shape"] else None),
-                    "traffic_source": offline["ball_query_traffic_bytes"].get("source"),
-                    "launches": len(bq), "avg_ms": round(ms, 4), "algorithmic_bytes": alg,
-                    "query_only": {"avg_ms": round(ms_q, 4), "achieved": round(alg / (ms_q * 1e-3) / 1e9, 2),
-                                   "frac": round(alg / (ms_q * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
-                    "grid_build": {"avg_ms": round(ms_b, 4), "launches_per_step": len(builds) / max(a.steps, 1),
-                                   "shared_by": "ogc_knn_clamped_cells (k-NN of the smoothness term) and ogc_ball_query_cells"},
-                    # per-launch event pairs read ~4.6 us with nothing between them (two marker packets): the same launches
-                    # with that floor removed, which is what the kernel trace of this command shows (profiles/)
-                    "event_pair_floor_ms": round(pair_floor_ms, 5),
-                    "floor_removed": (lambda q, bld: {"avg_ms": round(q + 0.5 * bld, 4), "query_ms": round(q, 4), "build_ms": round(bld, 4),
-                                                      "achieved": round(alg / ((q + 0.5 * bld) * 1e-3) / 1e9, 2),
-                                                      "frac": round(alg / ((q + 0.5 * bld) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)})(
-                        max(ms_q - pair_floor_ms, 1e-6), max(ms_b - pair_floor_ms, 0.0) if shared else 0.0),
-                    "isolated": None if isolated_ms is None else {
-                        "avg_ms": round(isolated_ms, 4), "achieved": round(alg / (isolated_ms * 1e-3) / 1e9, 2),
-                        "frac": round(alg / (isolated_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                        "note": "the stand-alone operator ogc_ball_query (its own grid build + query), 20 back-to-back "
-                                "launches on an idle GPU after the timed region"},
-                    "shape": {"B": b_, "N": n_, "M": m_, "nsample": ns_},
-                    "note": "algorithmic bytes = B*(12M + 12N + 4M*nsample) (SURVEY 8d) / mean duration (HIP events on the launch "
-                            "stream, inside the timed steps) of the query launch + half of the grid build it shares with the k-NN "
-                            "search; the exact cell-list search tests ~N/60 candidates per centre, so the all-pairs figure of "
-                            "8*B*N*M flop no longer describes the work done.  A pair of HIP events reads event_pair_floor_ms with "
-                            "NOTHING between them (measured live, idle GPU): achieved / frac / avg_ms are the raw readings, "
-                            "floor_removed the same launches with that floor taken off, which is what the rocprofv3 kernel "
-                            "statistics of this command show (profiles/rNN_bench_kernel_stats.csv of the newest round; tools/bench_ops.py has the "
-                            "idle-GPU table)",
-                    "all_pairs_equivalent_tpairs_per_s": round(b_ * n_ * m_ / (ms * 1e-3) / 1e12, 2)}
-        others = {}
-        for name in ("ogc_knn_clamped", "ogc_knn_clamped_cells", "ogc_cell_grid_build", "ogc_furthest_point_sampling",
-                     "ogc_furthest_point_sampling_chain"):
-            if name in durs:
-                per = {}
-                for d, dims in durs[name]:
-                    per.setdefault(str(dims[:4]), []).append(d)
-                others[name] = {k: round(sum(v) / len(v), 4) for k, v in per.items()}
         out = {
             "metric": "point-clouds/sec (8192 pts) segnet fwd+bwd",
             "value": round(clouds_per_step * a.steps * world / elapsed, 3),
@@ -810,12 +868,15 @@ def main():
                                    "+ bwd + Adam, %d samples x 4 views x %d pts per GPU" % (a.batch, a.npoint),
                        "clouds_per_step_per_gpu": clouds_per_step, "n_point": a.npoint, "n_slot": 10,
                        "parallelism": "dp%d" % world, "optimizer_stepped": bool(stepped),
-                       "peak_hbm_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+                       "peak_hbm_gib": round(peak_hbm / 2 ** 30, 2),
                        "loss": {k: round(v, 5) for k, v in loss_dict.items()}},
-            "roofline": roof,
-            "kernel_ms": others,
             "launch_thread_ms_per_step": round(issued / a.steps * 1e3, 3),
         }
+        if not a.full:
+            print(json.dumps(out), flush=True)
+    if rank == 0 and a.full:
+        offline = load_offline()
+        out["roofline"], out["kernel_ms"] = launch_readings(timer, offline, a, isolated_ms, pair_floor_ms)
         out.update(extras)
         out["fps_note"] = ("levels 2-3 of the encoder cost ~10 us in ms_per_step because the synthetic uniform clouds are free "
                            "of exact fp32 distance ties (the chain shortcut, DESIGN.md); ms_per_step_all_fps_rounds is the same "

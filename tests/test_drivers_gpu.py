@@ -141,7 +141,7 @@ def test_bench_under_one_process_rccl_launcher():
     """`python -m torch.distributed.run --nproc-per-node 1 bench.py --gpus 1`: backend nccl (= RCCL), FlatDataParallel with
     the collective forced on, barrier + MAX-over-ranks timing.  The JSON line must parse, carry the collective's
     payload, and the step must cost what the un-launched step costs (the all-reduce of 2.4 MB is tens of microseconds)."""
-    args = ["--gpus", "1", "--steps", "12", "--warmup", "5", "--no-cpu-baseline"]
+    args = ["--gpus", "1", "--steps", "12", "--warmup", "5", "--full", "--no-cpu-baseline"]   # (--full: the collective's timing)
     plain = _bench(args, launcher=False)
     dist_ = _bench(args, launcher=True)
     for r in (plain, dist_):
@@ -161,7 +161,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     other ranks never joined, i.e. a hang on the first real multi-GPU run); exactly one JSON line, whole-job throughput."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29700 + os.getpid() % 200), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
-           "--warmup", "2"]
+           "--warmup", "2", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OGC_BENCH_SHARE_GPU="1", OGC_BENCH_BACKEND="gloo")
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -173,3 +173,31 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     # whole-job value: both ranks' clouds over the slower rank's time
     assert abs(r["value"] - 2 * r["config"]["clouds_per_step_per_gpu"] / (r["ms_per_step"] * 1e-3)) <= 0.01 * r["value"]
     assert "cpu_baseline" not in r and "ms_per_step_with_h2d" not in r      # single-GPU readings: N = 1 only
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run: exactly the timed steps asked for, the headline keys and none of --full's readings.  With
+    --dump-outputs: the loss terms, optimizer flag and gradients of the step on the last timed batch from the seeded weights, as
+    float .npy files, and two runs with the same arguments write the same outputs to rounding (gradients are summed with atomic
+    adds: 2.5e-6 of an array's largest value measured, losses bit-equal)."""
+    dumps = []
+    for run in range(2):
+        out = str(tmp_path / ("dump%d" % run))
+        r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", out], launcher=False)
+        assert r["steps"] == 3 and r["warmup"] == 2 and r["unit"] == "point-clouds/s" and r["higher_is_better"] is True
+        assert r["dtype"] == "f32" and r["ms_per_step"] > 0
+        assert abs(r["value"] - r["config"]["clouds_per_step_per_gpu"] / (r["ms_per_step"] * 1e-3)) <= 0.01 * r["value"]
+        for key in ("roofline", "kernel_ms", "offline", "cpu_baseline", "cpu_ops", "ms_per_step_with_h2d", "config2_ogcdr_bf16"):
+            assert key not in r, key
+        dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))})
+    first, second = dumps
+    assert sorted(first) == sorted(second)
+    assert all(x.dtype in (np.float32, np.float64) and np.isfinite(x).all() for x in first.values())
+    assert sum(x.nbytes for x in first.values()) <= 64 * 2 ** 20
+    assert float(first["stepped"]) == 1.0 and set(first) >= {"loss_" + k for k in r["config"]["loss"]}
+    grads = [k for k in first if k.startswith("grad.")]
+    assert sum(first[k].size for k in grads) == 597248
+    for k in first:
+        x, y = first[k].astype(np.float64), second[k].astype(np.float64)
+        assert np.abs(x - y).max() <= 1e-4 * np.abs(x).max(), k
