@@ -1,4 +1,5 @@
-// grid.h — shared declarations of the cell-list acceleration (grid.hip) used by ball_query.hip.
+// grid.h — what knn.hip and ball_query.hip see of the cell-list acceleration (grid.hip: the build; grid_ball_query.hip,
+// grid_knn.hip: the searches; grid_dev.h: what those three share).
 #pragma once
 #include <hip/hip_runtime.h>
 

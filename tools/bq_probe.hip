@@ -1,10 +1,12 @@
-// Development probe for the cell-list ball query (ogc_amd/csrc/grid.hip compiled with OGC_GRID_PROBE): the C4 loss shape
+// Development probe for the cell-list ball query (the cell-grid sources compiled with OGC_GRID_PROBE): the C4 loss shape
 // (16 clouds x 8192 points in a 60 x 4 x 80 box, radius 2, 64 samples), build and query timed apart with HIP events, cycle
 // stamps of the build's phases and cycle sums of the query's phases.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I ogc_amd/csrc -I include tools/bq_probe.hip -o /tmp/bq_probe
 #define OGC_GRID_PROBE 1
 #include "../ogc_amd/csrc/api.hip"
 #include "../ogc_amd/csrc/grid.hip"
+#include "../ogc_amd/csrc/grid_ball_query.hip"
+#include "../ogc_amd/csrc/grid_knn.hip"
 #include <vector>
 
 int main(int argc, char **argv) {
@@ -22,13 +24,12 @@ int main(int argc, char **argv) {
     hipEvent_t e0, e1, e2; hipEventCreate(&e0); hipEventCreate(&e1); hipEventCreate(&e2);
     for (int i = 0; i < 5; ++i) if (ogc_ball_query_grid(B, N, N, radius, NS, xyz, xyz, idx, s) != 0) { printf("unsupported\n"); return 1; }
     hipStreamSynchronize(s);
-    const int stride_cells = GRID_MAX_CELLS + 1;
-    const size_t bytes_hdr = (sizeof(GridHdr) * B + 255) / 256 * 256;
-    const size_t bytes_cs = (sizeof(int) * (size_t)B * stride_cells + 255) / 256 * 256;
-    char *ws = static_cast<char *>(ogc_workspace(s, bytes_hdr + bytes_cs + sizeof(float4) * (size_t)B * N));
-    GridHdr *hdrs = reinterpret_cast<GridHdr *>(ws);
-    int *cell_start = reinterpret_cast<int *>(ws + bytes_hdr);
-    float4 *sorted_pts = reinterpret_cast<float4 *>(ws + bytes_hdr + bytes_cs);
+    const int stride_cells = STRIDE_CELLS;
+    const GridLayout L(B, N);
+    void *ws = ogc_workspace(s, L.total());
+    GridHdr *hdrs = L.hdrs(ws);
+    int *cell_start = L.cell_start(ws);
+    float4 *sorted_pts = L.sorted_pts(ws);
     std::vector<int> ref((size_t)B * N * NS), out((size_t)B * N * NS);
     const int IT = 50;
     size_t bad_total = 0;
