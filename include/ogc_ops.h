@@ -47,8 +47,8 @@ enum {
  * points): ogc_gather_xyz_pair, ogc_flow_advance, ogc_linear_cn, ogc_gru_reset, ogc_gru_blend,
  * ogc_soft_corr_flow, ogc_three_nn_weights; ogc_furthest_point_sampling_chain accepts temp == NULL.  0.2.2: the `_h` entry points
  * (activations of the shared MLPs stored as bf16; see "16-bit activations" at the end of this header).  0.2.4: ogc_set_deterministic /
- * ogc_get_deterministic.  0.2.5: ogc_group_linear_fwd_direct. */
-#define OGC_VERSION 205
+ * ogc_get_deterministic.  0.2.5: ogc_group_linear_fwd_direct.  0.2.6: ogc_rigid_icp. */
+#define OGC_VERSION 206
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
  * operation (what all parity tests pin).  1: this is libogc_ops_fmad.so, the same library with the search kernels (FPS, kNN,
@@ -225,6 +225,21 @@ int ogc_adam_step(int n_tensors, int n_chunks, const long long *table, const int
  * 0 where S contains NaN/inf (then R = I — the reference's `valid_batches` rule, :38-42), else 1.
  * One thread per matrix, Jacobi eigen-solve of S^T S in fp64. */
 int ogc_kabsch_rotation(int nb, const float *S, float *R, int *valid, ogc_stream_t stream);
+
+/* Batched classical point-to-point ICP, every iteration inside one launch.  Replaces utils/icp_util.py:73-124 `icp` (sklearn's
+ * nearest-neighbour search + numpy's SVD on the CPU, once per iteration), the ego-motion fit of test_flow_kittisf.py:103.
+ * src, dst (B,n,3) f32 — one n for both, as the reference asserts; init_pose (B,4,4) f64 row-major or NULL; T (B,4,4) f64
+ * row-major out; distances (B,n) f64 out: nearest-neighbour distances of the last search; iters (B) i32 out: the reference's
+ * returned `i` (the loop index at the break, or max_iterations - 1).
+ *   src <- init_pose src;  per iteration: nearest dst point of every src point (lower index on exact ties), best-fit rigid step
+ *   between the two centred sets (SVD of the 3x3 cross-covariance, last row of V^T negated when det R < 0), src <- step src, stop
+ *   when |prev_error - mean(distances of this search)| < tolerance;  T = best fit from the ORIGINAL src to the moved src.
+ * Arithmetic in fp64 on the widened fp32 inputs, as numpy does for the reference; sums in a fixed order (bit-identical from run to
+ * run).  One workgroup per pair, dst in LDS: n <= OGC_ICP_MAX_POINTS (OGC_ERR_INVALID_ARG beyond, and for n < 3 or
+ * max_iterations < 1).  B == 0 is a no-op. */
+#define OGC_ICP_MAX_POINTS 4096
+int ogc_rigid_icp(int B, int n, const float *src, const float *dst, const double *init_pose, int max_iterations, double tolerance,
+                  double *T, double *distances, int *iters, ogc_stream_t stream);
 
 /* Grouping with relative coordinates in front, in one output tensor.  Replaces, in QueryAndGroup.forward
  *   pointnet2/pointnet2.py:284-296:  grouped_xyz = group(xyz^T, idx) - new_xyz^T[..., None];

@@ -364,6 +364,14 @@ def kabsch_rotation_wrapper(nb, S, R, valid=None):
     _run("ogc_kabsch_rotation", S, nb, _f(S, "S"), _f(R, "R"), 0 if valid is None else _i(valid, "valid"))
 
 
+def rigid_icp_wrapper(b, n, src, dst, init_pose, max_iterations, tolerance, T, distances, iters):
+    """Point-to-point ICP of b pairs of (n, 3) clouds in one launch (ogc_rigid_icp): T (b, 4, 4) f64, distances (b, n) f64 of the
+    last search, iters (b,) i32; init_pose (b, 4, 4) f64 or None."""
+    _run("ogc_rigid_icp", src, b, n, _f(src, "src"), _f(dst, "dst"),
+         0 if init_pose is None else _check(init_pose, torch.float64, "init_pose"), int(max_iterations), float(tolerance),
+         _check(T, torch.float64, "T"), _check(distances, torch.float64, "distances"), _i(iters, "iters"))
+
+
 def group_concat_wrapper(b, c, n, npoints, nsample, xyz, new_xyz, points, idx, out):
     """out = cat([xyz[idx] - new_xyz, points[idx]], dim=1) (ogc_group_concat); points may be None when c == 0."""
     _run("ogc_group_concat", xyz, b, c, n, npoints, nsample, _f(xyz, "xyz"), _f(new_xyz, "new_xyz"),

@@ -86,3 +86,50 @@ def make_sequence(T, N, K, seed=1234, outdoor=True, device="cpu"):
         pcs.append(pc)
         segms.append(segm)
     return torch.stack(pcs).to(device), torch.stack(segms).to(device), torch.stack(flows).to(device)
+
+
+def make_kitti_raw_scene(N, seed=1234, ground_frac=0.3, n_cluster=48):
+    """One full-resolution KITTI-SF style pair as the "processed" layout stores it (datasets/dataset_kittisf.py:73-76): pc1,
+    pc2 (N, 3) with points in correspondence, one labelling segm (N,).  A static world — clusters of points above a ground
+    sheet at y = -1.65 +- 0.05, i.e. below the -1.4 m the flow-prediction driver cuts at — seen under a small ego-motion
+    (rotation about y, translation mostly along z), so the flow pc2 - pc1 is one exact rigid flow.  Also returns the 4x4
+    motion, float64."""
+    g = torch.Generator().manual_seed(seed)
+    n_ground = int(N * ground_frac)
+    n_obj = N - n_ground
+    centres = (torch.rand(n_cluster, 3, generator=g) - 0.5) * torch.tensor([50.0, 0.0, 50.0]) + torch.tensor([0.0, 0.5, 0.0])
+    which = torch.randint(n_cluster, (n_obj,), generator=g)
+    obj = centres[which] + torch.randn(n_obj, 3, generator=g) * torch.tensor([0.6, 0.5, 0.6])
+    obj[:, 1] = obj[:, 1].clamp(min=-1.2)
+    ground = (torch.rand(n_ground, 3, generator=g) - 0.5) * torch.tensor([60.0, 0.1, 60.0]) + torch.tensor([0.0, -1.65, 0.0])
+    pc1 = torch.cat([obj, ground])[torch.randperm(N, generator=g)]
+    sign = 1.0 if torch.rand(1, generator=g).item() < 0.5 else -1.0
+    angle = sign * (0.02 + 0.02 * torch.rand(1, generator=g))
+    shift = torch.tensor([0.3, 0.02, 0.4]) * (torch.rand(3, generator=g) - 0.5) * 2 + torch.tensor([0.0, 0.0, 0.8])
+    T = torch.eye(4, dtype=torch.float64)
+    T[:3, :3], T[:3, 3] = _rot_y(angle)[0].double(), shift.double()
+    pc2 = (pc1.double() @ T[:3, :3].T + T[:3, 3]).float()
+    return pc1.contiguous(), pc2.contiguous(), torch.zeros(N, dtype=torch.int64), T
+
+
+def write_kitti_processed_root(root, n_scenes, n_points, seed=1000, split="val"):
+    """`n_scenes` scenes of make_kitti_raw_scene under <root>/processed/%06d/{pc1,pc2,segm}.npy and the split file
+    <root>/<split>.txt listing their ids — what KITTISceneFlowDataset(root, mapping, downsampled=False) reads.
+    Returns (path of the split file, [4x4 motions])."""
+    import os
+
+    import numpy as np
+    ids, motions = [], []
+    for i in range(n_scenes):
+        pc1, pc2, segm, T = make_kitti_raw_scene(n_points, seed=seed + i)
+        d = os.path.join(root, "processed", "%06d" % i)
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "pc1.npy"), pc1.numpy())
+        np.save(os.path.join(d, "pc2.npy"), pc2.numpy())
+        np.save(os.path.join(d, "segm.npy"), segm.numpy())
+        ids.append("%06d" % i)
+        motions.append(T.numpy())
+    mapping = os.path.join(root, split + ".txt")
+    with open(mapping, "w") as f:
+        f.write("\n".join(ids) + "\n")
+    return mapping, motions
