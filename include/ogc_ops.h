@@ -47,8 +47,9 @@ enum {
  * points): ogc_gather_xyz_pair, ogc_flow_advance, ogc_linear_cn, ogc_gru_reset, ogc_gru_blend,
  * ogc_soft_corr_flow, ogc_three_nn_weights; ogc_furthest_point_sampling_chain accepts temp == NULL.  0.2.2: the `_h` entry points
  * (activations of the shared MLPs stored as bf16; see "16-bit activations" at the end of this header).  0.2.4: ogc_set_deterministic /
- * ogc_get_deterministic.  0.2.5: ogc_group_linear_fwd_direct.  0.2.6: ogc_rigid_icp. */
-#define OGC_VERSION 206
+ * ogc_get_deterministic.  0.2.5: ogc_group_linear_fwd_direct.  0.2.6: ogc_rigid_icp.
+ * 0.2.7: ogc_ground_plane_fit. */
+#define OGC_VERSION 207
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
  * operation (what all parity tests pin).  1: this is libogc_ops_fmad.so, the same library with the search kernels (FPS, kNN,
@@ -240,6 +241,23 @@ int ogc_kabsch_rotation(int nb, const float *S, float *R, int *valid, ogc_stream
 #define OGC_ICP_MAX_POINTS 4096
 int ogc_rigid_icp(int B, int n, const float *src, const float *dst, const double *init_pose, int max_iterations, double tolerance,
                   double *T, double *distances, int *iters, ogc_stream_t stream);
+
+/* Batched ground-plane fitting, seed, every fit and every retry inside one launch.  Replaces utils/gpf_util.py:45-66, the loop of
+ * `ground_plane_fitting` (numpy + scikit-spatial's Plane.best_fit on the CPU), the ground removal of test_flow_waymo.py:157-174.
+ * pc (B,n,3) f32; plane (B,6) f64 out: centre, unit normal with a vertical_axis component >= 0; is_ground (B,n) i32 out, 0/1;
+ * attempts (B) i32 out: the fits started (1 when the first succeeds).
+ *   lpr = mean of the n_lpr smallest heights (coordinate vertical_axis);  selection = height < lpr + thresh_seed;  n_iter times:
+ *   centre = mean of the selection, normal = eigenvector of the smallest eigenvalue of its 3x3 scatter,
+ *   selection = |(p - centre) . normal| < thresh_dist.  A fit fails on fewer than 3 selected points, on a scatter that is not
+ *   finite, or on a selection of rank below 2: l2 <= l1 * count * DBL_EPSILON for the scatter's eigenvalues l1 >= l2 >= l3
+ *   (numpy.linalg.matrix_rank's rule applied at the resolution a scatter matrix has).  Then thresh_seed += 0.05 (repeated addition
+ *   in double) and the cloud starts again from the seed; once the sum exceeds 0.8 it gives up: is_ground and plane all zero.
+ * Arithmetic in fp64 on the widened fp32 inputs; sums in a fixed order (bit-identical from run to run).  One workgroup per
+ * cloud, a thread's points in registers: 3 <= n <= OGC_GPF_MAX_POINTS, 1 <= n_lpr < n, n_iter >= 1, vertical_axis in 0..2
+ * (OGC_ERR_INVALID_ARG otherwise, nothing launched).  B == 0 is a no-op. */
+#define OGC_GPF_MAX_POINTS 8192
+int ogc_ground_plane_fit(int B, int n, const float *pc, int n_iter, int n_lpr, double thresh_seed, double thresh_dist,
+                         int vertical_axis, double *plane, int *is_ground, int *attempts, ogc_stream_t stream);
 
 /* Grouping with relative coordinates in front, in one output tensor.  Replaces, in QueryAndGroup.forward
  *   pointnet2/pointnet2.py:284-296:  grouped_xyz = group(xyz^T, idx) - new_xyz^T[..., None];

@@ -1,5 +1,6 @@
 // svd3.h — the fp64 3x3 "Kabsch rotation" R = V diag(1, 1, det(V U^T)) U^T of S = U diag(s) V^T as a device function, shared by
-// kabsch.hip (one thread per cross-covariance of the weighted-Kabsch fit) and rigid_icp.hip (one fit per ICP iteration).
+// kabsch.hip (one thread per cross-covariance of the weighted-Kabsch fit) and rigid_icp.hip (one fit per ICP iteration), and the
+// symmetric eigen-solve of ground_plane.hip (ogc_sym_eig3, at the end) on the same Jacobi rotation.
 //
 // Cyclic Jacobi eigen-solve of S^T S (six sweeps; three reach machine precision for 3x3), U recovered column by column
 // (with Gram-Schmidt completion for vanishing singular values), and the product formed from the two leading singular pairs
@@ -105,5 +106,35 @@ __device__ inline bool ogc_kabsch3(const double (&S)[3][3], double (&R)[3][3]) {
     return true;
 }
 
+template <int A, int B> // eigenpair B in front of eigenpair A when its eigenvalue is larger
+__device__ inline void eig_order(double (&lam)[3], double (&V)[3][3]) {
+    if (lam[B] > lam[A]) {
+        const double t = lam[A]; lam[A] = lam[B]; lam[B] = t;
+        for (int r = 0; r < 3; ++r) { const double v = V[r][A]; V[r][A] = V[r][B]; V[r][B] = v; }
+    }
+}
+
+// Eigen-decomposition of a symmetric S (finite; the caller scales it to max |entry| = 1): eigenvalues descending in lam, the
+// matching unit eigenvectors in the columns of V.  The same six cyclic Jacobi sweeps as above (ground_plane.hip: the plane
+// normal is column 2).  An exactly zero off-diagonal entry is left alone, so a scatter with exact zero rows keeps exact zero
+// eigenvalues.
+__device__ inline void ogc_sym_eig3(const double (&S)[3][3], double (&lam)[3], double (&V)[3][3]) {
+    double A[3][3], W[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) A[r][c] = S[r][c];
+    for (int sweep = 0; sweep < 6; ++sweep) {
+        jacobi_rot(A, W, 0, 1);
+        jacobi_rot(A, W, 0, 2);
+        jacobi_rot(A, W, 1, 2);
+    }
+    for (int j = 0; j < 3; ++j) {
+        lam[j] = A[j][j];
+        for (int r = 0; r < 3; ++r) V[r][j] = W[r][j];
+    }
+    // sorted with constant indices only: an array indexed through a run-time permutation leaves the registers
+    eig_order<0, 1>(lam, V);
+    eig_order<0, 2>(lam, V);
+    eig_order<1, 2>(lam, V);
+}
 
 } // namespace

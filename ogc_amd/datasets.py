@@ -13,6 +13,10 @@ one directory tree:
                              OGC-DR layout under %06d.npy.  NOT pinned against the reference's class: it imports pyquaternion
                              (utils/sapien_util.py), which this image lacks — tests/test_sapien_reader.py checks the flows against
                              the rigid motions applied directly
+  WaymoOpenDataset           <root>/data/<sequence>/{pc,segm,semantic_segm}_%04d.npy and the backward flows flow_%04d_%04d.npy
+                             (t, t - 1), a split file listing the sequences (datasets/dataset_waymo.py:19-181); predicted flows
+                             <root>/flow_preds/<name>/<sequence>/flow_%04d_%04d.npy.  A sample id is (sequence, t, t - 1); with
+                             downsampled=False the four items are lists of two frames with their own numbers of points
 
 A sample is (pcs (t, N, 3) f32, segms (t, N) i32, flows (t, N, 3) f32, valids (t, N) f32), t = 2 frames, or 4 with
 `aug_transform` (two random similarity transforms of the pair, utils/data_util.py:140-195).  The one-hot label variant of the
@@ -28,13 +32,14 @@ from .utils import flow_store
 from .utils.data_util import augment_transform, compress_label_id
 
 
-def _finish(pcs, segms, flows, decentralize, aug_transform, aug_transform_args):
-    """Common tail of both readers: centring, label compression, augmentation, dtypes (dataset_kittisf.py:95-122)."""
+def _finish(pcs, segms, flows, decentralize, aug_transform, aug_transform_args, valids=None):
+    """Common tail of the readers: centring, label compression, augmentation, dtypes (dataset_kittisf.py:95-122).  `valids`:
+    per-point validity of the two frames where the reader filters its labels (Waymo), all ones otherwise."""
     pcs, segms, flows = np.stack(pcs, 0), np.stack(segms, 0), np.stack(flows, 0)
     if decentralize:
         pcs = pcs - pcs.mean(1).mean(0)
     segms = compress_label_id(np.reshape(segms, -1)).reshape(2, -1)
-    valids = np.ones_like(segms, dtype=np.float32)
+    valids = np.ones_like(segms, dtype=np.float32) if valids is None else np.stack(valids, 0)
     if aug_transform:
         pcs, flows = augment_transform(pcs, flows, aug_transform_args)
         segms = np.concatenate((segms, segms), 0)
@@ -90,6 +95,93 @@ class KITTISceneFlowDataset(Dataset):
             d = os.path.join(save_root, self.data_ids[idx])
             os.makedirs(d, exist_ok=True)
             np.save(os.path.join(d, "flow%d.npy" % (k + 1)), flow_pred[i])
+
+
+class WaymoOpenDataset(Dataset):
+    """Reference: datasets/dataset_waymo.py:19-181.  Waymo carries backward scene flow only, so the samples of a sequence of T
+    frames are the pairs (t, t - 1), t = 1 .. T - 1, and both entries of `flows` are that one flow.  `select_frame` names a json
+    file with the sample ids to use instead; `ignore_class_ids` / `ignore_npoint_thresh` send the points of those semantic
+    classes / of objects smaller than that to label 0 and mark them invalid."""
+
+    def __init__(self, data_root, mapping_path, downsampled=False, select_frame=None, sampled_interval=1, predflow_path=None,
+                 decentralize=False, aug_transform=False, aug_transform_args=None, ignore_class_ids=(), ignore_npoint_thresh=0):
+        import json
+        self.data_root = os.path.join(data_root, "data")
+        with open(mapping_path, "r") as f:
+            self.sequence_list = [line.strip() for line in f if line.strip()]
+        self.downsampled = downsampled
+        if select_frame is not None:
+            with open(select_frame, "r") as f:
+                self.data_ids = [(str(seq), int(a), int(b)) for seq, a, b in json.load(f)]
+        else:
+            self.data_ids = self._make_dataset(sampled_interval)
+        self.predflow_path = os.path.join(data_root, "flow_preds", predflow_path) if predflow_path is not None else None
+        self.decentralize = decentralize
+        self.aug_transform, self.aug_transform_args = aug_transform, aug_transform_args
+        self.ignore_class_ids, self.ignore_npoint_thresh = list(ignore_class_ids), ignore_npoint_thresh
+
+    def _make_dataset(self, sampled_interval):
+        """Listed sequences that are not on disk are passed over (`n_skipped` counts them)."""
+        import glob
+        data_ids, self.n_skipped = [], 0
+        for entry in self.sequence_list:
+            name = os.path.splitext(entry)[0]          # the split files list the .tfrecord names
+            d = os.path.join(self.data_root, name)
+            if not os.path.isdir(d):
+                self.n_skipped += 1
+                continue
+            n_frame = len(glob.glob(os.path.join(d, "pc_*")))
+            data_ids += [(name, t, t - 1) for t in range(1, n_frame)]
+        return data_ids[::sampled_interval] if sampled_interval > 1 else data_ids
+
+    def __len__(self):
+        return len(self.data_ids)
+
+    def _load_data(self, name, view1, view2):
+        d = os.path.join(self.data_root, name)
+        return tuple([np.load(os.path.join(d, "%s_%04d.npy" % (what, v))) for v in (view1, view2)]
+                     for what in ("pc", "segm", "semantic_segm"))
+
+    def _load_flow(self, name, view1, view2):
+        flow = np.load(os.path.join(self.data_root, name, "flow_%04d_%04d.npy" % (view1, view2)))
+        return [flow, flow]
+
+    def _load_predflow(self, name, view1, view2):
+        path = os.path.join(self.predflow_path, name, "flow_%04d_%04d.npy" % (view1, view2))
+        if not os.path.isfile(path):
+            raise FileNotFoundError("no predicted flow %s" % path)
+        flow = np.load(path)
+        return [flow, flow]
+
+    def filter_segm(self, segms, semantic_segms):
+        """-> (labels with the ignored points at 0, validity 0 / 1 int32), per frame (dataset_waymo.py:110-128)."""
+        filtered, valids = [], []
+        for segm, semantic in zip(segms, semantic_segms):
+            ids, sizes = np.unique(segm, return_counts=True)
+            ignore = np.logical_or(np.isin(semantic, self.ignore_class_ids),
+                                   np.isin(segm, ids[sizes < self.ignore_npoint_thresh]))
+            filtered.append(np.where(ignore, 0, segm).astype(segm.dtype))
+            valids.append(1 - ignore.astype(np.int32))
+        return filtered, valids
+
+    def __getitem__(self, sid):
+        name, view1, view2 = self.data_ids[sid]
+        pcs, segms, semantic_segms = self._load_data(name, view1, view2)
+        flows = (self._load_predflow if self.predflow_path is not None else self._load_flow)(name, view1, view2)
+        segms, valids = self.filter_segm(segms, semantic_segms)
+        if not self.downsampled:      # the full scans: two frames with their own numbers of points, as loaded
+            return pcs, segms, flows, valids
+        return _finish(pcs, segms, flows, self.decentralize, self.aug_transform, self.aug_transform_args, valids)
+
+    def _save_predflow(self, flow_pred, save_root, batch_size, n_frame=1, offset=0):
+        """flow_pred (B, N, 3): sample `(offset * batch_size + i) // n_frame` -> <save_root>/<sequence>/flow_%04d_%04d.npy
+        (dataset_waymo.py:169-181)."""
+        flow_pred = flow_pred.detach().cpu().numpy() if hasattr(flow_pred, "detach") else np.asarray(flow_pred)
+        for i in range(flow_pred.shape[0]):
+            name, view1, view2 = self.data_ids[(offset * batch_size + i) // n_frame]
+            d = os.path.join(save_root, name)
+            os.makedirs(d, exist_ok=True)
+            np.save(os.path.join(d, "flow_%04d_%04d.npy" % (view1, view2)), flow_pred[i])
 
 
 def compute_flow(pc1, segm1, pose1, pose2):

@@ -372,6 +372,13 @@ def rigid_icp_wrapper(b, n, src, dst, init_pose, max_iterations, tolerance, T, d
          _check(T, torch.float64, "T"), _check(distances, torch.float64, "distances"), _i(iters, "iters"))
 
 
+def ground_plane_fit_wrapper(b, n, pc, n_iter, n_lpr, thresh_seed, thresh_dist, vertical_axis, plane, is_ground, attempts):
+    """Ground planes of b clouds (n, 3) in one launch (ogc_ground_plane_fit): plane (b, 6) f64 centre | unit normal, is_ground
+    (b, n) i32, attempts (b,) i32."""
+    _run("ogc_ground_plane_fit", pc, b, n, _f(pc, "pc"), int(n_iter), int(n_lpr), float(thresh_seed), float(thresh_dist),
+         int(vertical_axis), _check(plane, torch.float64, "plane"), _i(is_ground, "is_ground"), _i(attempts, "attempts"))
+
+
 def group_concat_wrapper(b, c, n, npoints, nsample, xyz, new_xyz, points, idx, out):
     """out = cat([xyz[idx] - new_xyz, points[idx]], dim=1) (ogc_group_concat); points may be None when c == 0."""
     _run("ogc_group_concat", xyz, b, c, n, npoints, nsample, _f(xyz, "xyz"), _f(new_xyz, "new_xyz"),

@@ -133,3 +133,83 @@ def write_kitti_processed_root(root, n_scenes, n_points, seed=1000, split="val")
     with open(mapping, "w") as f:
         f.write("\n".join(ids) + "\n")
     return mapping, motions
+
+
+def _rot_y_np(angle):
+    import numpy as np
+    c, s = np.cos(angle), np.sin(angle)
+    return np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
+
+
+WAYMO_SHEET = (0.03, 0.02, -0.2)     # the ground of the synthetic Waymo world: y = 0.03 x + 0.02 z - 0.2 (metres)
+
+
+def make_waymo_sequence(n_frames, n_points, seed=2000, ground_frac=0.6, n_boxes=8):
+    """One synthetic Waymo-style sequence: a static world — boxes standing on a TILTED ground sheet (3 cm / m in x, 2 cm / m in
+    z, so that a height threshold alone mislabels part of the ground) — in front of and beside a sensor that drives along +z under known
+    poses (yaw and translation in the ground plane; y is up and the sensor stays at y = 0).  Guaranteed gaps: every ground point
+    lies within 0.1 m of the sheet, every other point at least 0.6 m above it (and above y = 0.35).  Every frame samples the
+    world anew with its own number of points (n_points +- 5 %), so frames are not in correspondence.
+    Returns a list of frames {pc (N, 3) f32 in sensor coordinates, segm (N,) i32 instance ids (0: ground), semantic_segm (N,)
+    i32 class ids (0: ground, 1 / 2: boxes), ground (N,) bool, pose (4, 4) f64 sensor-to-world}."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    a, b, c0 = WAYMO_SHEET
+    centres = np.stack([(rs.rand(n_boxes) - 0.5) * 40.0, np.zeros(n_boxes), 6.0 + rs.rand(n_boxes) * 22.0], 1)
+    sizes = np.stack([1.5 + 2.0 * rs.rand(n_boxes), 1.2 + 1.5 * rs.rand(n_boxes), 1.5 + 2.5 * rs.rand(n_boxes)], 1)
+    classes = 1 + (np.arange(n_boxes) % 4 == 3).astype(np.int32)
+    frames, yaw, position = [], 0.0, np.zeros(3)
+    for t in range(n_frames):
+        pose = np.eye(4)
+        pose[:3, :3], pose[:3, 3] = _rot_y_np(yaw), position
+        n = n_points + int(rs.randint(-(n_points // 20), n_points // 20 + 1))
+        n_ground = int(n * ground_frac)
+        # ground: uniform around the sensor, within 0.08 m of the sheet
+        gx = position[0] + (rs.rand(n_ground) - 0.5) * 60.0
+        gz = position[2] + (rs.rand(n_ground) - 0.5) * 60.0
+        ground = np.stack([gx, a * gx + b * gz + c0 + (rs.rand(n_ground) - 0.5) * 0.16, gz], 1)
+        # boxes: points inside their footprint, from 0.6 m above the sheet (and y = 0.35) upwards
+        which = rs.randint(n_boxes, size=n - n_ground)
+        bx = centres[which, 0] + (rs.rand(n - n_ground) - 0.5) * sizes[which, 0]
+        bz = centres[which, 2] + (rs.rand(n - n_ground) - 0.5) * sizes[which, 2]
+        by = np.maximum(a * bx + b * bz + c0 + 0.6, 0.35) + rs.rand(n - n_ground) * sizes[which, 1]
+        world = np.concatenate([ground, np.stack([bx, by, bz], 1)])
+        segm = np.concatenate([np.zeros(n_ground, np.int32), (which + 1).astype(np.int32)])
+        perm = rs.permutation(n)
+        world, segm = world[perm], segm[perm]
+        pc = ((world - position) @ pose[:3, :3]).astype(np.float32)         # R^T (w - t), row-wise
+        frames.append({"pc": pc, "segm": segm, "semantic_segm": np.where(segm > 0, classes[np.maximum(segm, 1) - 1], 0).astype(np.int32),
+                       "ground": segm == 0, "pose": pose})
+        yaw += (rs.rand() - 0.5) * 0.04
+        position = position + np.array([(rs.rand() - 0.5) * 0.2, 0.0, 0.6 + 0.4 * rs.rand()])
+    return frames
+
+
+def write_waymo_root(root, n_sequences, n_frames, n_points, seed=2000, split="val"):
+    """`n_sequences` sequences of make_waymo_sequence under <root>/data/seq_%04d/{pc,segm,semantic_segm,ground,pose}_%04d.npy
+    with the backward flows flow_%04d_%04d.npy (t, t - 1) — the rigid flow of frame t towards frame t - 1, the world being
+    static — and the split file <root>/<split>.txt: what WaymoOpenDataset(root, mapping) reads.
+    Returns (path of the split file, {sequence name: [4x4 poses]})."""
+    import os
+
+    import numpy as np
+    names, poses = [], {}
+    for k in range(n_sequences):
+        name = "seq_%04d" % k
+        frames = make_waymo_sequence(n_frames, n_points, seed=seed + k)
+        d = os.path.join(root, "data", name)
+        os.makedirs(d, exist_ok=True)
+        for t, frame in enumerate(frames):
+            for what in ("pc", "segm", "semantic_segm", "ground", "pose"):
+                np.save(os.path.join(d, "%s_%04d.npy" % (what, t)), frame[what])
+            if t >= 1:
+                p1, p2 = frame["pose"], frames[t - 1]["pose"]
+                rot, transl = p2[:3, :3].T @ p1[:3, :3], p2[:3, :3].T @ (p1[:3, 3] - p2[:3, 3])
+                pc = frame["pc"].astype(np.float64)
+                np.save(os.path.join(d, "flow_%04d_%04d.npy" % (t, t - 1)), (pc @ rot.T + transl - pc).astype(np.float32))
+        names.append(name)
+        poses[name] = [f["pose"] for f in frames]
+    mapping = os.path.join(root, split + ".txt")
+    with open(mapping, "w") as f:
+        f.write("\n".join(names) + "\n")
+    return mapping, poses
