@@ -48,8 +48,9 @@ enum {
  * ogc_soft_corr_flow, ogc_three_nn_weights; ogc_furthest_point_sampling_chain accepts temp == NULL.  0.2.2: the `_h` entry points
  * (activations of the shared MLPs stored as bf16; see "16-bit activations" at the end of this header).  0.2.4: ogc_set_deterministic /
  * ogc_get_deterministic.  0.2.5: ogc_group_linear_fwd_direct.  0.2.6: ogc_rigid_icp.
- * 0.2.7: ogc_ground_plane_fit. */
-#define OGC_VERSION 207
+ * 0.2.7: ogc_ground_plane_fit.
+ * 0.2.8: ogc_seg_eval. */
+#define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
  * operation (what all parity tests pin).  1: this is libogc_ops_fmad.so, the same library with the search kernels (FPS, kNN,
@@ -258,6 +259,32 @@ int ogc_rigid_icp(int B, int n, const float *src, const float *dst, const double
 #define OGC_GPF_MAX_POINTS 8192
 int ogc_ground_plane_fit(int B, int n, const float *pc, int n_iter, int n_lpr, double thresh_seed, double thresh_dist,
                          int vertical_axis, double *plane, int *is_ground, int *attempts, ogc_stream_t stream);
+
+/* Segmentation evaluation of a batch in one launch: everything metrics/seg_metric.py computes per sample (eval_segm :38-93,
+ * ClusteringMetrics :181-243) except the assignment, which ogc_lsap_maximize(B, 64, score) does next.  No host round trip.
+ * segm (B,n) i32 GT labels in [0, OGC_SEG_EVAL_MAX_LABELS); mask (B,n,k) f32 point-major; ignore_npoint_thresh >= 0.  Outputs:
+ *   hard (B,n) i32        arg-max over the k slots: the first maximum; a NaN counts as the maximum and the first NaN wins.
+ *   counts (B,64,k) i32   points with label g and arg-max slot p.  Rows are RAW labels; an absent label is an empty row.
+ *   pred_iou, confidence (B,k) f64, valid (B,k) i32, n_gt (B) i32   the AP table.  A GT object is ignored when 0 < size < thresh;
+ *       a prediction is invalid when strictly more than half of its points lie in ignored objects or nothing is left of it;
+ *       IoU = inter / (gt size + kept prediction size - inter) in fp64 on exact integers, maximum over the kept objects (0 when
+ *       none is kept); n_gt = kept objects.  confidence keeps the reference's quirk: the column of the j-th VALID slot is
+ *       summed over the points of the j-th PRESENT slot and divided by that slot's full size (an invalid slot takes the source
+ *       of the last valid one before it, or the first present slot).
+ *   score (B,64,64) f32   [g,p] = m / ((a_g + b_p - m) + 1e-8f) in float32, one rounding per operation, on the table whose rows
+ *       with size < thresh are zeroed when thresh > 0 (a_g, b_p: its row and column sums); zero in those rows, in rows past the
+ *       largest label and in columns >= k.
+ *   rows (B) i32          rows g <= largest label that are not zeroed: the divisor of the mean IoU.
+ *   ri (B) f64            (n_v^2 - sum a_g^2 - sum b_p^2 + 2 sum m^2) / n_v^2, the sums in 64-bit integers, then one fp64 division
+ *       of the two converted integers; NaN when n_v (the points left in the table) is 0.
+ *   status (B) i32        0 ok; bit 0: a label >= OGC_SEG_EVAL_MAX_LABELS was seen; bit 1: a negative label was seen.  Such a
+ *       sample has all its other outputs zeroed and does not touch its neighbours; nothing is indexed with such a label.
+ * Integer sums by LDS atomics, fp64 sums in a fixed order, no floating-point atomics: two calls give identical bits.
+ * 1 <= k <= 64, n >= 1, thresh >= 0, no null pointer (OGC_ERR_INVALID_ARG otherwise, nothing launched).  B == 0 is a no-op. */
+#define OGC_SEG_EVAL_MAX_LABELS 64
+int ogc_seg_eval(int B, int n, int k, const int *segm, const float *mask, int ignore_npoint_thresh, int *hard, int *counts,
+                 double *pred_iou, double *confidence, int *valid, int *n_gt, float *score, int *rows, double *ri, int *status,
+                 ogc_stream_t stream);
 
 /* Grouping with relative coordinates in front, in one output tensor.  Replaces, in QueryAndGroup.forward
  *   pointnet2/pointnet2.py:284-296:  grouped_xyz = group(xyz^T, idx) - new_xyz^T[..., None];

@@ -67,6 +67,7 @@ SIGNATURES = {
     "ogc_kabsch_rotation": [_int, _vp, _vp, _vp, _vp],
     "ogc_rigid_icp": [_int, _int, _vp, _vp, _vp, _int, _dbl, _vp, _vp, _vp, _vp],
     "ogc_ground_plane_fit": [_int, _int, _vp, _int, _int, _dbl, _dbl, _int, _vp, _vp, _vp, _vp],
+    "ogc_seg_eval": [_int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_lsap_maximize": [_int, _int, _vp, _vp, _vp],
     "ogc_rigid_moments": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_rigid_translation": [_int, _vp, _vp, _vp, _vp, _vp],
@@ -151,7 +152,7 @@ SIGNATURES["ogc_group_linear_fwd_direct_h"] = SIGNATURES["ogc_group_linear_fwd_d
 SIGNATURES["ogc_conv1x1_wgrad_xf_h"] = SIGNATURES["ogc_conv1x1_wgrad"]
 SIGNATURES["ogc_group_linear_fwd_pt_h"] = SIGNATURES["ogc_group_linear_fwd"]
 
-HEADER_VERSION = 207   # OGC_VERSION of include/ogc_ops.h the SIGNATURES table above was written against
+HEADER_VERSION = 208  # OGC_VERSION of include/ogc_ops.h the SIGNATURES table above was written against
 _lib = None
 _fns = {}  # entry point name -> bound ctypes function
 

@@ -18,6 +18,14 @@ one directory tree:
                              <root>/flow_preds/<name>/<sequence>/flow_%04d_%04d.npy.  A sample id is (sequence, t, t - 1); with
                              downsampled=False the four items are lists of two frames with their own numbers of points
 
+  KITTIDetectionDataset      <root>/downsampled/<id>/{pc,segm}.npy, a split file listing the ids (datasets/dataset_kittidet.py)
+  SemanticKITTIDataset       the same files; the ids are the sorted directory names whose first two characters are a sequence
+                             number in `sequence_list` (datasets/dataset_semantickitti.py).  Both are single-frame sets for
+                             evaluation (test_seg.py): the frame is duplicated to two views, the flows are zero
+
+Predicted segmentations (`_save_predsegm`, written by test_seg.py under <root>/segm_preds/<name>): int64 labels per frame as
+<id>/segm{1,2}.npy (KITTI-SF), <id>/segm_%02d.npy (OGC-DR; SAPIEN with <id> = %06d), <id>/segm.npy (KITTI-Det, SemanticKITTI).
+
 A sample is (pcs (t, N, 3) f32, segms (t, N) i32, flows (t, N, 3) f32, valids (t, N) f32), t = 2 frames, or 4 with
 `aug_transform` (two random similarity transforms of the pair, utils/data_util.py:140-195).  The one-hot label variant of the
 supervised baselines (`onehot_label`) is out of scope.  tests/golden/flow_store.npz pins files and samples against
@@ -45,6 +53,31 @@ def _finish(pcs, segms, flows, decentralize, aug_transform, aug_transform_args, 
         segms = np.concatenate((segms, segms), 0)
         valids = np.concatenate((valids, valids), 0)
     return pcs.astype(np.float32), segms.astype(np.int32), flows.astype(np.float32), valids.astype(np.float32)
+
+
+def _hard_labels(mask_or_hard):
+    """(B, N, K) soft masks -> their arg-max over K; (B, N) hard labels as they are; a tensor or an array -> numpy int64, what
+    numpy's argmax gives the reference (`mask[sid].argmax(1)`, dataset_kittisf.py:144-146)."""
+    x = mask_or_hard
+    if hasattr(x, "detach"):
+        x = x.detach()
+        x = (x.argmax(dim=2) if x.dim() == 3 else x).cpu().numpy()
+    else:
+        x = np.asarray(x)
+        x = x.argmax(2) if x.ndim == 3 else x
+    if x.ndim != 2:
+        raise ValueError("expected (B, N, K) masks or (B, N) labels, got shape %s" % (tuple(x.shape),))
+    return x.astype(np.int64)
+
+
+def _save_frame_labels(mask_or_hard, save_root, batch_size, n_frame, offset, scene_dir, file_name):
+    """Sample `offset * batch_size + i` of a loader over (scene, frame) pairs -> <save_root>/<scene_dir(idx)>/<file_name(k)>."""
+    hard = _hard_labels(mask_or_hard)
+    for i in range(hard.shape[0]):
+        idx, k = divmod(offset * batch_size + i, n_frame)
+        d = os.path.join(save_root, scene_dir(idx))
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, file_name(k)), hard[i])
 
 
 class KITTISceneFlowDataset(Dataset):
@@ -95,6 +128,11 @@ class KITTISceneFlowDataset(Dataset):
             d = os.path.join(save_root, self.data_ids[idx])
             os.makedirs(d, exist_ok=True)
             np.save(os.path.join(d, "flow%d.npy" % (k + 1)), flow_pred[i])
+
+    def _save_predsegm(self, mask_or_hard, save_root, batch_size, n_frame=1, offset=0):
+        """(B, N, K) masks or (B, N) hard labels -> <save_root>/<id>/segm<k + 1>.npy, int64 (dataset_kittisf.py:140-152)."""
+        _save_frame_labels(mask_or_hard, save_root, batch_size, n_frame, offset, lambda idx: self.data_ids[idx],
+                           lambda k: "segm%d.npy" % (k + 1))
 
 
 class WaymoOpenDataset(Dataset):
@@ -238,6 +276,11 @@ class OGCDynamicRoomDataset(Dataset):
             idx = offset * batch_size // n_frame + i
             np.save(os.path.join(save_root, self.data_ids[idx] + ".npy"), flow_pred[i * n_frame:(i + 1) * n_frame])
 
+    def _save_predsegm(self, mask_or_hard, save_root, batch_size, n_frame=1, offset=0):
+        """(B, N, K) masks or (B, N) hard labels -> <save_root>/<id>/segm_%02d.npy, int64 (dataset_ogcdr.py:160-172)."""
+        _save_frame_labels(mask_or_hard, save_root, batch_size, n_frame, offset, lambda idx: self.data_ids[idx],
+                           lambda k: "segm_%02d.npy" % k)
+
 
 def _rigid_inverse(m):
     """Inverse of a 4x4 rigid transform as (R^T, -R^T t) — what the reference's Isometry.inv() computes on (quaternion, t)
@@ -317,3 +360,65 @@ class SapienDataset(Dataset):
         for i in range(flow_pred.shape[0] // n_frame):
             idx = offset * batch_size // n_frame + i
             np.save(os.path.join(save_root, self._name(idx) + ".npy"), flow_pred[i * n_frame:(i + 1) * n_frame])
+
+    def _save_predsegm(self, mask_or_hard, save_root, batch_size, n_frame=1, offset=0):
+        """(B, N, K) masks or (B, N) hard labels -> <save_root>/%06d/segm_%02d.npy, int64 (dataset_sapien.py:158-170)."""
+        _save_frame_labels(mask_or_hard, save_root, batch_size, n_frame, offset, self._name, lambda k: "segm_%02d.npy" % k)
+
+
+class _SingleFrameDataset(Dataset):
+    """The sample contract of the two single-frame sets (dataset_kittidet.py:73-114, dataset_semantickitti.py:53-85): centring
+    on the frame's own mean, labels compressed per frame, the frame duplicated to two views, zero flows, valids of ones."""
+
+    def __len__(self):
+        return len(self.data_ids)
+
+    def _load_data(self, idx):
+        d = os.path.join(self.data_root, self.data_ids[idx])
+        return np.load(os.path.join(d, "pc.npy")), np.load(os.path.join(d, "segm.npy"))
+
+    def __getitem__(self, sid):
+        pc, segm = self._load_data(sid)
+        if self.decentralize:
+            pc = pc - pc.mean(0)
+        segm = compress_label_id(segm)
+        pcs, segms = np.stack([pc, pc], 0), np.stack([segm, segm], 0)
+        flows = np.zeros_like(pcs)
+        valids = np.ones_like(segms, dtype=np.float32)
+        if self.aug_transform:
+            pcs, flows = augment_transform(pcs, flows, self.aug_transform_args)
+            segms = np.concatenate((segms, segms), 0)
+            valids = np.concatenate((valids, valids), 0)
+        return pcs.astype(np.float32), segms.astype(np.int32), flows.astype(np.float32), valids.astype(np.float32)
+
+    def _save_predsegm(self, mask_or_hard, save_root, batch_size, n_frame=1, offset=0):
+        """(B, N, K) masks or (B, N) hard labels -> <save_root>/<id>/segm.npy, int64; sample `offset * batch_size + i`, whatever
+        n_frame (dataset_kittidet.py:117-129)."""
+        _save_frame_labels(mask_or_hard, save_root, batch_size, 1, offset, lambda idx: self.data_ids[idx],
+                           lambda k: "segm.npy")
+
+
+class KITTIDetectionDataset(_SingleFrameDataset):
+    """Reference: datasets/dataset_kittidet.py:9-129 (`onehot_label`, `load_prediction` and `load_confidence` belong to the
+    supervised baselines and are out of scope)."""
+
+    def __init__(self, data_root, mapping_path, decentralize=False, aug_transform=False, aug_transform_args=None):
+        self.data_root = os.path.join(data_root, "downsampled")
+        with open(mapping_path, "r") as f:
+            self.data_ids = f.read().strip().split("\n")
+        self.decentralize = decentralize
+        self.aug_transform, self.aug_transform_args = aug_transform, aug_transform_args
+
+
+class SemanticKITTIDataset(_SingleFrameDataset):
+    """Reference: datasets/dataset_semantickitti.py:9-100.  `sequence_list` None takes every frame (the reference leaves
+    `data_ids` undefined there)."""
+
+    def __init__(self, data_root, sequence_list=None, decentralize=False, aug_transform=False, aug_transform_args=None):
+        self.data_root = os.path.join(data_root, "downsampled")
+        data_ids = sorted(os.listdir(self.data_root))
+        if sequence_list is not None:
+            data_ids = [idx for idx in data_ids if int(idx[:2]) in sequence_list]
+        self.data_ids = data_ids
+        self.decentralize = decentralize
+        self.aug_transform, self.aug_transform_args = aug_transform, aug_transform_args

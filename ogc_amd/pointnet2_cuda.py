@@ -379,6 +379,17 @@ def ground_plane_fit_wrapper(b, n, pc, n_iter, n_lpr, thresh_seed, thresh_dist, 
          int(vertical_axis), _check(plane, torch.float64, "plane"), _i(is_ground, "is_ground"), _i(attempts, "attempts"))
 
 
+def seg_eval_wrapper(b, n, k, segm, mask, ignore_npoint_thresh, hard, counts, pred_iou, confidence, valid, n_gt, score, rows,
+                     ri, status):
+    """Segmentation evaluation of b samples in one launch (ogc_seg_eval): segm (b, n) i32, mask (b, n, k) f32 -> hard (b, n) i32,
+    counts (b, 64, k) i32, pred_iou / confidence (b, k) f64, valid (b, k) i32, n_gt (b,) i32, score (b, 64, 64) f32, rows (b,) i32,
+    ri (b,) f64, status (b,) i32."""
+    _run("ogc_seg_eval", mask, b, n, k, _i(segm, "segm"), _f(mask, "mask"), int(ignore_npoint_thresh), _i(hard, "hard"),
+         _i(counts, "counts"), _check(pred_iou, torch.float64, "pred_iou"), _check(confidence, torch.float64, "confidence"),
+         _i(valid, "valid"), _i(n_gt, "n_gt"), _f(score, "score"), _i(rows, "rows"), _check(ri, torch.float64, "ri"),
+         _i(status, "status"))
+
+
 def group_concat_wrapper(b, c, n, npoints, nsample, xyz, new_xyz, points, idx, out):
     """out = cat([xyz[idx] - new_xyz, points[idx]], dim=1) (ogc_group_concat); points may be None when c == 0."""
     _run("ogc_group_concat", xyz, b, c, n, npoints, nsample, _f(xyz, "xyz"), _f(new_xyz, "new_xyz"),

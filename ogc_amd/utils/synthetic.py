@@ -213,3 +213,48 @@ def write_waymo_root(root, n_sequences, n_frames, n_points, seed=2000, split="va
     with open(mapping, "w") as f:
         f.write("\n".join(names) + "\n")
     return mapping, poses
+
+
+LABELLED_LAYOUTS = ("kittisf", "kittidet", "semantickitti")
+SYNTHETIC_SEQUENCES = (0, 8, 12)   # synthetic frames cycle through these; test_seg evaluates sequences 0..10
+
+
+def write_labelled_root(root, layout, n_scenes, n_points, n_objects, seed=3000, split="val"):
+    """`n_scenes` outdoor scenes of make_scene_batch (objects = Voronoi cells of random centres, rigid motion per object) with
+    their labels, in the layout a segmentation data set of ogc_amd/datasets.py reads:
+      kittisf         <root>/data/%06d/{pc,segm,flow}{1,2}.npy, <root>/<split>.txt    (KITTISceneFlowDataset, downsampled=True)
+      kittidet        <root>/downsampled/%06d/{pc,segm}.npy, <root>/<split>.txt       (KITTIDetectionDataset; frame 1 only)
+      semantickitti   <root>/downsampled/<ss>_%06d/{pc,segm}.npy, ss cycling through SYNTHETIC_SEQUENCES, no split file
+    Labels are written as 2 * object + 1, with gaps, so that a reader has something to compress.
+    Returns (path of the split file or None, [ids])."""
+    import os
+
+    import numpy as np
+    if layout not in LABELLED_LAYOUTS:
+        raise KeyError("write_labelled_root covers %s, got %r" % (", ".join(LABELLED_LAYOUTS), layout))
+    ids = []
+    for i in range(n_scenes):
+        pcs, segms, flows, _ = make_scene_batch(1, n_points, n_objects, seed=seed + i, outdoor=True)
+        pcs, segms, flows = pcs[0].numpy(), (2 * segms[0] + 1).numpy().astype(np.int32), flows[0].numpy()
+        if layout == "kittisf":
+            name = "%06d" % i
+            d = os.path.join(root, "data", name)
+            os.makedirs(d, exist_ok=True)
+            for v in (0, 1):
+                np.save(os.path.join(d, "pc%d.npy" % (v + 1)), pcs[v])
+                np.save(os.path.join(d, "segm%d.npy" % (v + 1)), segms[v])
+                np.save(os.path.join(d, "flow%d.npy" % (v + 1)), flows[v])
+        else:
+            sequence = SYNTHETIC_SEQUENCES[i % len(SYNTHETIC_SEQUENCES)]
+            name = "%06d" % i if layout == "kittidet" else "%02d_%06d" % (sequence, i)
+            d = os.path.join(root, "downsampled", name)
+            os.makedirs(d, exist_ok=True)
+            np.save(os.path.join(d, "pc.npy"), pcs[0])
+            np.save(os.path.join(d, "segm.npy"), segms[0])
+        ids.append(name)
+    if layout == "semantickitti":
+        return None, ids
+    mapping = os.path.join(root, split + ".txt")
+    with open(mapping, "w") as f:
+        f.write("\n".join(ids) + "\n")
+    return mapping, ids
