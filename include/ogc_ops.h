@@ -49,7 +49,7 @@ enum {
  * (activations of the shared MLPs stored as bf16; see "16-bit activations" at the end of this header).  0.2.4: ogc_set_deterministic /
  * ogc_get_deterministic.  0.2.5: ogc_group_linear_fwd_direct.  0.2.6: ogc_rigid_icp.
  * 0.2.7: ogc_ground_plane_fit.
- * 0.2.8: ogc_seg_eval. */
+ * 0.2.8: ogc_seg_eval.  ogc_flow_eval added under 0.2.8: no prototype changed, and the number is pinned by a test of that release. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -285,6 +285,21 @@ int ogc_ground_plane_fit(int B, int n, const float *pc, int n_iter, int n_lpr, d
 int ogc_seg_eval(int B, int n, int k, const int *segm, const float *mask, int ignore_npoint_thresh, int *hard, int *counts,
                  double *pred_iou, double *confidence, int *valid, int *n_gt, float *score, int *rows, double *ri, int *status,
                  ogc_stream_t stream);
+
+/* Scene-flow metrics of a batch in one launch (metrics/flow_metric.py:16-24).  gt_flow, flow_pred (B,N,3) f32, contiguous.
+ * Per point, in fp32 with one rounding per operation: d = pred - gt, e = sqrtf((dx*dx + dy*dy) + dz*dz), s the same on gt,
+ * r = e / (s + (float)eps); strict: e < (float)t || r < 0.05f; relaxed: e < (float)(2t) || r < 0.1f; outlier: e > (float)(6t) ||
+ * r > 0.1f, t = epe_norm_thresh.  Outputs, which do not depend on their previous contents:
+ *   epe_sum (B) f64     the sum of e over the sample's points, formed in a fixed order (per-workgroup partials, one ordered
+ *                       finish; no floating-point atomics): identical bits from call to call and from process to process.
+ *   counts (B,3) i32    the sample's strict-accurate, relaxed-accurate and outlier points.
+ * A NaN satisfies no comparison and makes its own sample's epe_sum NaN; other samples are untouched.  One kernel launch, no
+ * allocation, no fill, no synchronisation: capturable.  Several workgroups per sample exchange their partials through a static
+ * table of the library: calls on DIFFERENT streams of one device must not overlap in time.
+ * B < 0, N < 1, epe_norm_thresh not finite or <= 0, eps not finite or < 0, a null pointer: OGC_ERR_INVALID_ARG, nothing
+ * launched.  B == 0 is a no-op whatever else is passed. */
+int ogc_flow_eval(int B, int N, const float *gt_flow, const float *flow_pred, double epe_norm_thresh, double eps,
+                  double *epe_sum, int *counts, ogc_stream_t stream);
 
 /* Grouping with relative coordinates in front, in one output tensor.  Replaces, in QueryAndGroup.forward
  *   pointnet2/pointnet2.py:284-296:  grouped_xyz = group(xyz^T, idx) - new_xyz^T[..., None];

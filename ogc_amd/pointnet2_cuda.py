@@ -390,6 +390,13 @@ def seg_eval_wrapper(b, n, k, segm, mask, ignore_npoint_thresh, hard, counts, pr
          _i(status, "status"))
 
 
+def flow_eval_wrapper(b, n, gt_flow, flow_pred, epe_norm_thresh, eps, epe_sum, counts):
+    """Scene-flow metrics of b samples in one launch (ogc_flow_eval): gt_flow, flow_pred (b, n, 3) f32 -> epe_sum (b,) f64 the
+    sum of the end-point errors, counts (b, 3) i32 the strict-accurate, relaxed-accurate and outlier points."""
+    _run("ogc_flow_eval", gt_flow, b, n, _f(gt_flow, "gt_flow"), _f(flow_pred, "flow_pred"), float(epe_norm_thresh), float(eps),
+         _check(epe_sum, torch.float64, "epe_sum"), _i(counts, "counts"))
+
+
 def group_concat_wrapper(b, c, n, npoints, nsample, xyz, new_xyz, points, idx, out):
     """out = cat([xyz[idx] - new_xyz, points[idx]], dim=1) (ogc_group_concat); points may be None when c == 0."""
     _run("ogc_group_concat", xyz, b, c, n, npoints, nsample, _f(xyz, "xyz"), _f(new_xyz, "new_xyz"),

@@ -258,3 +258,132 @@ def write_labelled_root(root, layout, n_scenes, n_points, n_objects, seed=3000, 
     with open(mapping, "w") as f:
         f.write("\n".join(ids) + "\n")
     return mapping, ids
+
+
+def _sequence_scene(n_frames, n_points, n_objects, seed):
+    """An object-scale scene for the two four-frame layouts: `n_objects` blobs in the unit cube (labels 1..n_objects) in front of
+    a static background (label 0, about a quarter of the points), every object under its own 4x4 object-to-world motion per
+    frame (a rotation of a few degrees about y and a shift of a few centimetres from frame to frame).  Every frame holds the
+    SAME canonical points in its own order.  Returns canon (N, 3) f64, label (N,) i32, motions (n_frames, n_objects, 4, 4) f64,
+    perms (n_frames, N)."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    label = rs.randint(0, n_objects + 1, size=n_points).astype(np.int32)
+    label[rs.rand(n_points) < 0.1] = 0
+    centres = (rs.rand(n_objects + 1, 3) - 0.5) * 0.8
+    canon = centres[label] + rs.randn(n_points, 3) * 0.06
+    canon[label == 0] = (rs.rand(int((label == 0).sum()), 3) - 0.5) * np.array([1.0, 0.05, 1.0]) - np.array([0.0, 0.5, 0.0])
+    motions = np.zeros((n_frames, n_objects, 4, 4))
+    yaw, shift = np.zeros(n_objects), centres[1:].copy()
+    for t in range(n_frames):
+        for k in range(n_objects):
+            motions[t, k] = np.eye(4)
+            motions[t, k, :3, :3], motions[t, k, :3, 3] = _rot_y_np(yaw[k]), shift[k]
+        yaw = yaw + (rs.rand(n_objects) - 0.5) * 2 * math.radians(8.0)
+        shift = shift + (rs.rand(n_objects, 3) - 0.5) * 0.1
+    perms = np.stack([rs.permutation(n_points) for _ in range(n_frames)])
+    return canon - np.where(label[:, None] > 0, centres[label], 0.0), label, motions, perms
+
+
+def _apply_4x4(m, pc):
+    return pc @ m[:3, :3].T + m[:3, 3]
+
+
+def write_ogcdr_root(root, n_scenes, n_points, n_objects=3, n_frames=4, seed=4000, split="val"):
+    """`n_scenes` scenes of `n_frames` frames in the OGC-DR layout: <root>/data/<id>/{pc,segm,pose}_%02d.npy — pc (N, 3) f32,
+    segm (N,) i32 (0: background), pose (n_objects, 4, 4) f64 object-to-world — and <root>/data/<split>.lst, exactly what
+    OGCDynamicRoomDataset(root, split) reads; the flow it computes from the poses moves every object rigidly onto its place in
+    the other frame.  Returns [ids]."""
+    import os
+
+    import numpy as np
+    ids = []
+    for i in range(n_scenes):
+        canon, label, motions, perms = _sequence_scene(n_frames, n_points, n_objects, seed + i)
+        name = "%08d" % i
+        d = os.path.join(root, "data", name)
+        os.makedirs(d, exist_ok=True)
+        for t in range(n_frames):
+            pc = canon.copy()
+            for k in range(n_objects):
+                pc[label == k + 1] = _apply_4x4(motions[t, k], canon[label == k + 1])
+            np.save(os.path.join(d, "pc_%02d.npy" % t), pc[perms[t]].astype(np.float32))
+            np.save(os.path.join(d, "segm_%02d.npy" % t), label[perms[t]])
+            np.save(os.path.join(d, "pose_%02d.npy" % t), motions[t])
+        ids.append(name)
+    with open(os.path.join(root, "data", split + ".lst"), "w") as f:
+        f.write("\n".join(ids) + "\n")
+    return ids
+
+
+def write_sapien_root(root, n_scenes, n_points, n_parts=3, n_frames=4, seed=5000, split="val"):
+    """`n_scenes` articulated objects of `n_parts` parts seen in `n_frames` frames in the SAPIEN layout: <root>/meta.json
+    {split: [integer ids]} and <root>/data/%06d.npz with pc (V, N, 3) f32 in each frame's CAMERA coordinates, segm (V, N) i32
+    (0: no part) and trans {"cam": (V, 4, 4), part id: (V, 4, 4)} (camera-to-world, part-to-world) — exactly what
+    SapienDataset(root, split) reads; its flow is cam_b^-1 . M_b . M_a^-1 . cam_a applied per part.  Points of no part are given
+    to part 1 here: the reader leaves their flow at zero, which would not be a motion of the moving camera's frame.
+    Returns [ids]."""
+    import json
+    import os
+
+    import numpy as np
+    ids = []
+    os.makedirs(os.path.join(root, "data"), exist_ok=True)
+    for i in range(n_scenes):
+        canon, label, motions, perms = _sequence_scene(n_frames, n_points, n_parts, seed + i)
+        label = np.where(label == 0, 1, label).astype(np.int32)
+        rs = np.random.RandomState(seed + 7919 * (i + 1))
+        cams = np.zeros((n_frames, 4, 4))
+        for t in range(n_frames):
+            cams[t] = np.eye(4)
+            cams[t, :3, :3] = _rot_y_np((rs.rand() - 0.5) * 2 * math.radians(10.0))
+            cams[t, :3, 3] = (rs.rand(3) - 0.5) * 0.1
+        pcs = np.zeros((n_frames, n_points, 3))
+        for t in range(n_frames):
+            inv = np.linalg.inv(cams[t])
+            for k in range(n_parts):
+                sel = label == k + 1
+                pcs[t, sel] = _apply_4x4(inv, _apply_4x4(motions[t, k], canon[sel]))
+        # one order for all frames: the npz holds (V, N) arrays and the reader indexes them by frame
+        trans = {k + 1: motions[:, k].copy() for k in range(n_parts)}
+        trans["cam"] = cams
+        np.savez(os.path.join(root, "data", "%06d.npz" % i), pc=pcs[:, perms[0]].astype(np.float32),
+                 segm=np.stack([label[perms[0]]] * n_frames), trans=np.array(trans, dtype=object))
+        ids.append(i)
+    with open(os.path.join(root, "meta.json"), "w") as f:
+        json.dump({split: ids}, f)
+    return ids
+
+
+def write_kitti_downsampled_root(full_root, down_root, n_points, predflow=None, seed=6000, split="val"):
+    """The down-sampled twin of a root written by write_kitti_processed_root, in the layout KITTISceneFlowDataset(down_root,
+    mapping, downsampled=True) reads: per scene `n_points` random points of each frame (their own subset per frame) as
+    <down_root>/data/<id>/{pc,segm,flow}{1,2}.npy, the flows being the scan's own pc2 - pc1 and pc1 - pc2 at those points, and
+    <down_root>/<split>.txt.  With `predflow` the same flows are stored once more as predictions,
+    <down_root>/flow_preds/<predflow>/<id>/flow{1,2}.npy.  Returns (path of the split file, [ids])."""
+    import os
+
+    import numpy as np
+
+    from . import flow_store
+    with open(os.path.join(full_root, split + ".txt")) as f:
+        ids = f.read().strip().split("\n")
+    rs = np.random.RandomState(seed)
+    for name in ids:
+        src = os.path.join(full_root, "processed", name)
+        pc1, pc2, segm = (np.load(os.path.join(src, what + ".npy")) for what in ("pc1", "pc2", "segm"))
+        d = os.path.join(down_root, "data", name)
+        os.makedirs(d, exist_ok=True)
+        flows = []
+        for v, (pc, other) in enumerate(((pc1, pc2), (pc2, pc1))):
+            sel = rs.choice(pc.shape[0], size=min(n_points, pc.shape[0]), replace=False)
+            np.save(os.path.join(d, "pc%d.npy" % (v + 1)), pc[sel])
+            np.save(os.path.join(d, "segm%d.npy" % (v + 1)), segm[sel])
+            np.save(os.path.join(d, "flow%d.npy" % (v + 1)), other[sel] - pc[sel])
+            flows.append(other[sel] - pc[sel])
+        if predflow is not None:
+            flow_store.save_pair(os.path.join(down_root, "flow_preds", predflow), name, flows[0], flows[1])
+    mapping = os.path.join(down_root, split + ".txt")
+    with open(mapping, "w") as f:
+        f.write("\n".join(ids) + "\n")
+    return mapping, ids
