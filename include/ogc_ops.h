@@ -741,7 +741,8 @@ int ogc_group_norm_maxpool_fwd_stats(int b, int c, int p, int s, int groups, flo
  * [0, nsample) of the first neighbour attaining it.  ogc_group_norm_pool_extremes turns those and the statistics into
  * exactly what ogc_group_norm_maxpool_fwd_stats computes from the full tensor — out (b, c, p), argmax, mean, rstd —
  * so the backward pass (ogc_group_norm_maxpool_bwd) is unchanged.  (Two DIFFERENT raw values that round to the same
- * activation are told apart here and not there; with gamma == 0 both report neighbour 0.) */
+ * activation are told apart here and not there; with gamma == 0, and where the ReLU gates the whole neighbourhood, both
+ * report neighbour 0.) */
 int ogc_conv1x1_gemm_affine_pool(int b, int M, int K, int hw, int relu, int groups, int nsample, const float *w,
                                  const float *in, const float *pa, const float *pb, const float *next_gamma,
                                  float *out, double *stats, float *yext, int *aext, ogc_stream_t stream);

@@ -390,7 +390,9 @@ __global__ __launch_bounds__(GN_THREADS) void gn_pool_extremes_kernel(int c, int
         float y = fmaf(a, yext[base + pr], bb);
         if (RELU) y = fmaxf(y, 0.f);
         out[base + pr] = y;
-        arg[base + pr] = a != 0.f ? aext[base + pr] : 0;   // a == 0: every neighbour gives bb, the first wins the tie
+        // a == 0: every neighbour gives bb; extreme gated by the ReLU: every neighbour gives 0 — the first wins the tie, as in
+        // gn_apply_maxpool_kernel
+        arg[base + pr] = a != 0.f && (!RELU || y > 0.f) ? aext[base + pr] : 0;
     }
 }
 
@@ -408,7 +410,8 @@ __global__ __launch_bounds__(GN_THREADS) void gn_maxpool_bwd_sums_kernel(int c, 
     __shared__ double smem[2 * GN_THREADS / 64];
     const int b = blockIdx.z, ch = blockIdx.y;
     // xext holds x at the neighbourhood's EXTREME; arg is that position unless the channel's scale is zero
-    // (gn_pool_extremes_kernel: arg = 0 there, as the pass over the full tensor would have it): gather for such a channel
+    // (gn_pool_extremes_kernel: arg = 0 there, as the pass over the full tensor would have it): gather for such a channel.
+    // (arg = 0 also where the ReLU gates the whole row, but g = 0 there and the product with it is 0 either way.)
     if (xext && !(rstd[b * groups + ch / (c / groups)] * gamma[ch] != 0.f)) xext = nullptr;
     const size_t base = ((size_t)b * c + ch) * p;
     double ds = 0.0, db = 0.0;
