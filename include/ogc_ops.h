@@ -49,7 +49,9 @@ enum {
  * (activations of the shared MLPs stored as bf16; see "16-bit activations" at the end of this header).  0.2.4: ogc_set_deterministic /
  * ogc_get_deterministic.  0.2.5: ogc_group_linear_fwd_direct.  0.2.6: ogc_rigid_icp.
  * 0.2.7: ogc_ground_plane_fit.
- * 0.2.8: ogc_seg_eval.  ogc_flow_eval added under 0.2.8: no prototype changed, and the number is pinned by a test of that release. */
+ * 0.2.8: ogc_seg_eval.  ogc_flow_eval added under 0.2.8: no prototype changed, and the number is pinned by a test of that release.
+ * The supervised mask loss (ogc_sup_loss_ws_doubles, ogc_sup_match_cost, ogc_sup_mask_loss_fwd / _bwd) likewise: new entry points
+ * only, and two tests of 0.2.8 pin the number. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -300,6 +302,51 @@ int ogc_seg_eval(int B, int n, int k, const int *segm, const float *mask, int ig
  * launched.  B == 0 is a no-op whatever else is passed. */
 int ogc_flow_eval(int B, int N, const float *gt_flow, const float *flow_pred, double epe_norm_thresh, double eps,
                   double *epe_sum, int *counts, ogc_stream_t stream);
+
+/* The supervised mask loss (losses/seg_loss_sup.py) without its (B, N, K, K) tensors.  Throughout: mask (B,n,k) f32 point-major,
+ * the model's soft masks; gt_mask (B,n,k) f32 with entries in [0, 1], not necessarily 0/1 (batch_segm_to_mask_withconf scales
+ * columns by a confidence); valid (B,n) f32, or NULL for all ones.  The element function e(p, t) is what
+ * F.binary_cross_entropy(p, t, reduction='none') computes in float32, (t - 1) * max(log1p(-p), -100) - t * max(log(p), -100), so
+ * p == 0 with t == 1 gives exactly 100; with use_focal it is multiplied by (1 - p_t)^gamma, p_t = t p + (1 - t)(1 - p), then by
+ * alpha_t = alpha t + (1 - alpha)(1 - t) when alpha >= 0, in the order of FocalLoss.forward.  gamma == 2 is a plain square, any
+ * other gamma powf.  One rounding per operation.  A p that is NaN or outside [0, 1] makes every sum it enters NaN; it never traps.
+ * Sums over points are fp64 in a fixed order (per-workgroup partials of OGC_SUP_LOSS_TILE points each, then one ordered finish),
+ * no floating-point atomics: two calls give identical bits.  The partials pass through ws, a caller-owned buffer of at least
+ * ogc_sup_loss_ws_doubles(B, n, k) doubles (0 for arguments outside the limits) whose previous contents do not matter; the
+ * library holds no static table, so calls on different streams are independent.  No allocation, no fill, no synchronisation:
+ * capturable (two launches per forward entry point, one for the backward).
+ * Limits of all three: 1 <= k <= OGC_SUP_LOSS_MAX_K, n >= 1, gamma finite and >= 1, alpha not NaN (gamma and alpha are checked
+ * whatever use_focal says), no null pointer other than valid: OGC_ERR_INVALID_ARG otherwise, nothing launched.  B == 0 is a no-op.
+ *
+ * ogc_sup_match_cost: the two tables CrossEntropyLoss / FocalLoss.match_cost and DiceLoss.match_cost are built from, both
+ *   (B,k,k) f32, rows = predicted slot i, columns = GT slot j:
+ *     cost_ce[b,i,j]   = (1/n) sum_n valid * e(mask[b,n,i], gt_mask[b,n,j])
+ *     cost_dice[b,i,j] = 1 - (2 sum_n p t v + 1) / (sum_n p v + sum_n t v + 1)
+ *   per-point terms in float32 ((p * t) * v, p * v, t * v), the sums and the final expressions in fp64, rounded once.  (The
+ *   reference's DiceLoss.match_cost then takes the mean of the WHOLE (B,k,k) table; that is left to the caller.)
+ * ogc_sup_mask_loss_fwd: col4row (B,k) i32, predicted slot i is matched to GT column col4row[b,i] (perm = eye[col_ind] and
+ *   einsum('bij,bnj->bni') of the reference; the permuted labels are never written).
+ *     sums (B,k,4) f64 = {sum v * e(p_i, t_col), sum p t v, sum p v, sum t v}
+ *     terms (2) f32    = {l_ce: sum of sums[..., 0] / (B n k); l_dice: mean over (B,k) of 1 - (2 inter + 1) / (a + b + 1)}, in fp64
+ *                        from sums, rounded once.
+ *   An entry of col4row outside [0, k) (ogc_lsap_maximize writes -1 for a cost holding a NaN) makes that slot's sums and both
+ *   terms NaN; nothing is indexed with it.
+ * ogc_sup_mask_loss_bwd: grad_mask (B,n,k) f32 = grad_out[0] * d(w_ce * l_ce + w_dice * l_dice) / d mask, grad_out one f32 in
+ *   device memory.  BCE as torch's backward, (p - t) / max((1 - p) p, 1e-12) * v / (B n k), exactly 0 where p == t in {0, 1};
+ *   the focal factor's derivative goes through p_t; the Dice part is formed from the saved sums.  fp64 arithmetic on the
+ *   widened inputs, rounded once; one element-wise kernel.  Labels are detached: no gradient for gt_mask.  A slot whose
+ *   col4row entry is outside [0, k) gets NaN. */
+#define OGC_SUP_LOSS_MAX_K 32
+#define OGC_SUP_LOSS_TILE 64
+long long ogc_sup_loss_ws_doubles(int B, int n, int k);
+int ogc_sup_match_cost(int B, int n, int k, const float *mask, const float *gt_mask, const float *valid, int use_focal,
+                       double alpha, double gamma, double *ws, float *cost_ce, float *cost_dice, ogc_stream_t stream);
+int ogc_sup_mask_loss_fwd(int B, int n, int k, const float *mask, const float *gt_mask, const float *valid, const int *col4row,
+                          int use_focal, double alpha, double gamma, double *ws, double *sums, float *terms,
+                          ogc_stream_t stream);
+int ogc_sup_mask_loss_bwd(int B, int n, int k, const float *mask, const float *gt_mask, const float *valid, const int *col4row,
+                          int use_focal, double alpha, double gamma, const double *sums, double w_ce, double w_dice,
+                          const float *grad_out, float *grad_mask, ogc_stream_t stream);
 
 /* Grouping with relative coordinates in front, in one output tensor.  Replaces, in QueryAndGroup.forward
  *   pointnet2/pointnet2.py:284-296:  grouped_xyz = group(xyz^T, idx) - new_xyz^T[..., None];

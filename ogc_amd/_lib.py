@@ -70,6 +70,10 @@ SIGNATURES = {
     "ogc_seg_eval": [_int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_flow_eval": [_int, _int, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp],
     "ogc_lsap_maximize": [_int, _int, _vp, _vp, _vp],
+    "ogc_sup_loss_ws_doubles": [_int, _int, _int],
+    "ogc_sup_match_cost": [_int, _int, _int, _vp, _vp, _vp, _int, _dbl, _dbl, _vp, _vp, _vp, _vp],
+    "ogc_sup_mask_loss_fwd": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _dbl, _dbl, _vp, _vp, _vp, _vp],
+    "ogc_sup_mask_loss_bwd": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _dbl, _dbl, _vp, _dbl, _dbl, _vp, _vp, _vp],
     "ogc_rigid_moments": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_rigid_translation": [_int, _vp, _vp, _vp, _vp, _vp],
     "ogc_rigid_blend": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -185,6 +189,7 @@ def load():
                               (LIB_PATH, "contracted (fma)" if L.ogc_distance_contracted() else "un-contracted"))
         L.ogc_slot_masks_ws_floats.restype = ctypes.c_longlong
         L.ogc_cell_grid_bytes.restype = ctypes.c_longlong
+        L.ogc_sup_loss_ws_doubles.restype = ctypes.c_longlong
         L.ogc_last_error.restype = ctypes.c_char_p
         L.ogc_set_deterministic(1 if DETERMINISTIC else 0)
         _lib = L

@@ -27,9 +27,11 @@ Predicted segmentations (`_save_predsegm`, written by test_seg.py under <root>/s
 <id>/segm{1,2}.npy (KITTI-SF), <id>/segm_%02d.npy (OGC-DR; SAPIEN with <id> = %06d), <id>/segm.npy (KITTI-Det, SemanticKITTI).
 
 A sample is (pcs (t, N, 3) f32, segms (t, N) i32, flows (t, N, 3) f32, valids (t, N) f32), t = 2 frames, or 4 with
-`aug_transform` (two random similarity transforms of the pair, utils/data_util.py:140-195).  The one-hot label variant of the
-supervised baselines (`onehot_label`) is out of scope.  tests/golden/flow_store.npz pins files and samples against
-the reference's classes.
+`aug_transform` (two random similarity transforms of the pair, utils/data_util.py:140-195).  With `onehot_label=True` — what the
+supervised trainer (train_seg_sup.py) asks of KITTISceneFlowDataset, KITTIDetectionDataset, OGCDynamicRoomDataset and
+SapienDataset — segms is instead (t, N, max_n_object) f32, one-hot over the ranks of the compressed labels, and valids is 0 at
+the points of objects smaller than `ignore_npoint_thresh` (the two KITTI sets; utils/data_util.py: batch_segm_to_mask).
+tests/golden/flow_store.npz and sup_readers.npz pin files and samples against the reference's classes.
 """
 import os
 
@@ -37,16 +39,29 @@ import numpy as np
 from torch.utils.data import Dataset
 
 from .utils import flow_store
-from .utils.data_util import augment_transform, compress_label_id
+from .utils.data_util import augment_transform, batch_segm_to_mask, compress_label_id
 
 
-def _finish(pcs, segms, flows, decentralize, aug_transform, aug_transform_args, valids=None):
+def _one_hot(segms, max_n_object, ignore_npoint_thresh):
+    """The one-hot variant of a sample's labels (dataset_kittisf.py:106-109): (t, N, max_n_object) f32 masks and valids."""
+    assert max_n_object > 0, 'max_n_object must be above 0!'
+    return batch_segm_to_mask(segms, max_n_object, ignore_npoint_thresh)
+
+
+def _finish(pcs, segms, flows, decentralize, aug_transform, aug_transform_args, valids=None, onehot=None):
     """Common tail of the readers: centring, label compression, augmentation, dtypes (dataset_kittisf.py:95-122).  `valids`:
-    per-point validity of the two frames where the reader filters its labels (Waymo), all ones otherwise."""
+    per-point validity of the two frames where the reader filters its labels (Waymo), all ones otherwise.  `onehot`:
+    (max_n_object, ignore_npoint_thresh) of a reader built with onehot_label=True, else None."""
     pcs, segms, flows = np.stack(pcs, 0), np.stack(segms, 0), np.stack(flows, 0)
     if decentralize:
         pcs = pcs - pcs.mean(1).mean(0)
     segms = compress_label_id(np.reshape(segms, -1)).reshape(2, -1)
+    if onehot is not None:
+        segms, valids = _one_hot(segms, *onehot)
+        if aug_transform:
+            pcs, flows = augment_transform(pcs, flows, aug_transform_args)
+            segms, valids = np.concatenate((segms, segms), 0), np.concatenate((valids, valids), 0)
+        return pcs.astype(np.float32), segms.astype(np.float32), flows.astype(np.float32), valids.astype(np.float32)
     valids = np.ones_like(segms, dtype=np.float32) if valids is None else np.stack(valids, 0)
     if aug_transform:
         pcs, flows = augment_transform(pcs, flows, aug_transform_args)
@@ -82,7 +97,8 @@ def _save_frame_labels(mask_or_hard, save_root, batch_size, n_frame, offset, sce
 
 class KITTISceneFlowDataset(Dataset):
     def __init__(self, data_root, mapping_path, downsampled=False, view_sels=[[0, 1]], predflow_path=None, decentralize=False,
-                 aug_transform=False, aug_transform_args=None):
+                 aug_transform=False, aug_transform_args=None, onehot_label=False, max_n_object=15, ignore_npoint_thresh=0):
+        self.onehot_label, self.max_n_object, self.ignore_npoint_thresh = onehot_label, max_n_object, ignore_npoint_thresh
         self.data_root = os.path.join(data_root, "data" if downsampled else "processed")
         with open(mapping_path, "r") as f:
             self.data_ids = f.read().strip().split("\n")
@@ -117,7 +133,8 @@ class KITTISceneFlowDataset(Dataset):
         pcs, segms, flows = self._load_data(idx, view_sel)
         if self.predflow_path is not None:
             flows = self._load_predflow(idx, view_sel)
-        return _finish(pcs, segms, flows, self.decentralize, self.aug_transform, self.aug_transform_args)
+        return _finish(pcs, segms, flows, self.decentralize, self.aug_transform, self.aug_transform_args,
+                       onehot=(self.max_n_object, self.ignore_npoint_thresh) if self.onehot_label else None)
 
     def _save_predflow(self, flow_pred, save_root, batch_size, n_frame=1, offset=0):
         """flow_pred (B, N, 3): sample `offset * batch_size + i` of a loader over (scene, frame) pairs -> <save_root>/<id>/flow<k>.npy
@@ -235,7 +252,8 @@ def compute_flow(pc1, segm1, pose1, pose2):
 
 class OGCDynamicRoomDataset(Dataset):
     def __init__(self, data_root, split="train", view_sels=[[0, 1]], predflow_path=None, decentralize=False, aug_transform=False,
-                 aug_transform_args=None):
+                 aug_transform_args=None, onehot_label=False, max_n_object=8):
+        self.onehot_label, self.max_n_object = onehot_label, max_n_object
         self.data_root = os.path.join(data_root, "data")
         self.split = split
         with open(os.path.join(self.data_root, split + ".lst"), "r") as f:
@@ -266,7 +284,8 @@ class OGCDynamicRoomDataset(Dataset):
             flows = flow_store.load_pair(self.predflow_path, self.data_ids[idx], view_sel, self.pf_view_sels)
         else:
             flows = [compute_flow(pcs[0], segms[0], poses[0], poses[1]), compute_flow(pcs[1], segms[1], poses[1], poses[0])]
-        return _finish(pcs, segms, flows, self.decentralize, self.aug_transform, self.aug_transform_args)
+        return _finish(pcs, segms, flows, self.decentralize, self.aug_transform, self.aug_transform_args,
+                       onehot=(self.max_n_object, 0) if self.onehot_label else None)
 
     def _save_predflow(self, flow_pred, save_root, batch_size, n_frame=1, offset=0):
         """flow_pred (B, N, 3), the n_frame ordered pairs of a scene adjacent -> <save_root>/<id>.npy (n_frame, N, 3)
@@ -304,11 +323,12 @@ def compute_part_flow(base_pc, base_segms, base_cam, base_motions, dest_cam, des
 
 
 class SapienDataset(Dataset):
-    """Reference: datasets/dataset_sapien.py:22-170 (the one-hot label variant of the supervised baselines is out of scope)."""
+    """Reference: datasets/dataset_sapien.py:22-170."""
 
     def __init__(self, data_root, split="train", view_sels=[[0, 1]], predflow_path=None, decentralize=False, aug_transform=False,
-                 aug_transform_args=None):
+                 aug_transform_args=None, onehot_label=False, max_n_object=8):
         import json
+        self.onehot_label, self.max_n_object = onehot_label, max_n_object
         self.data_root = os.path.join(data_root, "data")
         with open(os.path.join(data_root, "meta.json")) as f:
             self.meta = json.load(f)
@@ -351,7 +371,8 @@ class SapienDataset(Dataset):
             cam = lambda v: np.asarray(trans["cam"][v], dtype=np.float64)
             flows = [compute_part_flow(pcs[0], segms[0], cam(a), motions(a), cam(b), motions(b)),
                      compute_part_flow(pcs[1], segms[1], cam(b), motions(b), cam(a), motions(a))]
-        return _finish(list(pcs), list(segms), flows, self.decentralize, self.aug_transform, self.aug_transform_args)
+        return _finish(list(pcs), list(segms), flows, self.decentralize, self.aug_transform, self.aug_transform_args,
+                       onehot=(self.max_n_object, 0) if self.onehot_label else None)
 
     def _save_predflow(self, flow_pred, save_root, batch_size, n_frame=1, offset=0):
         """flow_pred (B, N, 3), the n_frame ordered pairs of a scene adjacent -> <save_root>/%06d.npy (n_frame, N, 3)
@@ -368,7 +389,9 @@ class SapienDataset(Dataset):
 
 class _SingleFrameDataset(Dataset):
     """The sample contract of the two single-frame sets (dataset_kittidet.py:73-114, dataset_semantickitti.py:53-85): centring
-    on the frame's own mean, labels compressed per frame, the frame duplicated to two views, zero flows, valids of ones."""
+    on the frame's own mean, labels compressed per frame, the frame duplicated to two views, zero flows, valids of ones.
+    `onehot_label` (KITTI-Det): one-hot masks and the valids of batch_segm_to_mask instead (dataset_kittidet.py:95-112)."""
+    onehot_label, max_n_object, ignore_npoint_thresh = False, 18, 0
 
     def __len__(self):
         return len(self.data_ids)
@@ -384,12 +407,16 @@ class _SingleFrameDataset(Dataset):
         segm = compress_label_id(segm)
         pcs, segms = np.stack([pc, pc], 0), np.stack([segm, segm], 0)
         flows = np.zeros_like(pcs)
-        valids = np.ones_like(segms, dtype=np.float32)
+        if self.onehot_label:
+            segms, valids = _one_hot(segms, self.max_n_object, self.ignore_npoint_thresh)
+        else:
+            valids = np.ones_like(segms, dtype=np.float32)
         if self.aug_transform:
             pcs, flows = augment_transform(pcs, flows, self.aug_transform_args)
             segms = np.concatenate((segms, segms), 0)
             valids = np.concatenate((valids, valids), 0)
-        return pcs.astype(np.float32), segms.astype(np.int32), flows.astype(np.float32), valids.astype(np.float32)
+        return (pcs.astype(np.float32), segms.astype(np.float32 if self.onehot_label else np.int32), flows.astype(np.float32),
+                valids.astype(np.float32))
 
     def _save_predsegm(self, mask_or_hard, save_root, batch_size, n_frame=1, offset=0):
         """(B, N, K) masks or (B, N) hard labels -> <save_root>/<id>/segm.npy, int64; sample `offset * batch_size + i`, whatever
@@ -399,10 +426,12 @@ class _SingleFrameDataset(Dataset):
 
 
 class KITTIDetectionDataset(_SingleFrameDataset):
-    """Reference: datasets/dataset_kittidet.py:9-129 (`onehot_label`, `load_prediction` and `load_confidence` belong to the
-    supervised baselines and are out of scope)."""
+    """Reference: datasets/dataset_kittidet.py:9-129.  `load_prediction` / `load_confidence` (training on the predicted
+    segmentations of another model, with batch_segm_to_mask_withconf) stay out: no driver of this package uses them."""
 
-    def __init__(self, data_root, mapping_path, decentralize=False, aug_transform=False, aug_transform_args=None):
+    def __init__(self, data_root, mapping_path, decentralize=False, aug_transform=False, aug_transform_args=None,
+                 onehot_label=False, max_n_object=18, ignore_npoint_thresh=0):
+        self.onehot_label, self.max_n_object, self.ignore_npoint_thresh = onehot_label, max_n_object, ignore_npoint_thresh
         self.data_root = os.path.join(data_root, "downsampled")
         with open(mapping_path, "r") as f:
             self.data_ids = f.read().strip().split("\n")

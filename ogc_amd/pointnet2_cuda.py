@@ -478,6 +478,43 @@ def lsap_maximize_wrapper(np_, k, score, col4row):
     _run("ogc_lsap_maximize", score, np_, k, _f(score, "score"), _i(col4row, "col4row"))
 
 
+SUP_LOSS_MAX_K = 32   # OGC_SUP_LOSS_MAX_K
+SUP_LOSS_TILE = 64    # OGC_SUP_LOSS_TILE: points per workgroup of the supervised-loss sums
+
+
+def sup_loss_workspace(b, n, k, device):
+    """The scratch buffer the two forward entry points of the supervised mask loss exchange their partial sums through
+    (ogc_sup_loss_ws_doubles): caller-owned, contents irrelevant, may be reused by calls on the same stream."""
+    return torch.empty(max(int(_lib.load().ogc_sup_loss_ws_doubles(b, n, k)), 1), dtype=torch.float64, device=device)
+
+
+def _focal(focal):
+    """(use_focal, alpha, gamma) of the C ABI from None (plain BCE) or an (alpha, gamma) pair."""
+    return (0, -1.0, 2.0) if focal is None else (1, float(focal[0]), float(focal[1]))
+
+
+def sup_match_cost_wrapper(b, n, k, mask, gt_mask, valid, focal, ws, cost_ce, cost_dice):
+    """The (b, k, k) cross-entropy / focal and Dice matching costs of the supervised mask loss (ogc_sup_match_cost): mask, gt_mask
+    (b, n, k) f32, valid (b, n) f32 or None, focal None or (alpha, gamma), ws from sup_loss_workspace."""
+    _run("ogc_sup_match_cost", mask, b, n, k, _f(mask, "mask"), _f(gt_mask, "gt_mask"), 0 if valid is None else _f(valid, "valid"),
+         *_focal(focal), _check(ws, torch.float64, "ws"), _f(cost_ce, "cost_ce"), _f(cost_dice, "cost_dice"))
+
+
+def sup_mask_loss_fwd_wrapper(b, n, k, mask, gt_mask, valid, col4row, focal, ws, sums, terms):
+    """The matched loss (ogc_sup_mask_loss_fwd): col4row (b, k) i32 -> sums (b, k, 4) f64, terms (2,) f32 = {l_ce, l_dice}."""
+    _run("ogc_sup_mask_loss_fwd", mask, b, n, k, _f(mask, "mask"), _f(gt_mask, "gt_mask"),
+         0 if valid is None else _f(valid, "valid"), _i(col4row, "col4row"), *_focal(focal), _check(ws, torch.float64, "ws"),
+         _check(sums, torch.float64, "sums"), _f(terms, "terms"))
+
+
+def sup_mask_loss_bwd_wrapper(b, n, k, mask, gt_mask, valid, col4row, focal, sums, w_ce, w_dice, grad_out, grad_mask):
+    """grad_mask (b, n, k) f32 = grad_out * d(w_ce * l_ce + w_dice * l_dice) / d mask (ogc_sup_mask_loss_bwd); grad_out a
+    one-element f32 device tensor."""
+    _run("ogc_sup_mask_loss_bwd", mask, b, n, k, _f(mask, "mask"), _f(gt_mask, "gt_mask"),
+         0 if valid is None else _f(valid, "valid"), _i(col4row, "col4row"), *_focal(focal),
+         _check(sums, torch.float64, "sums"), float(w_ce), float(w_dice), _f(grad_out, "grad_out"), _f(grad_mask, "grad_mask"))
+
+
 def sym_eigvals_wrapper(nb, k, A, w):
     """Ascending eigenvalues of (nb, k, k) symmetric float64 matrices (ogc_sym_eigvals)."""
     _run("ogc_sym_eigvals", A, nb, k, _check(A, torch.float64, "A"), _check(w, torch.float64, "w"))

@@ -1,4 +1,5 @@
-"""Thin callers of the operators used by data preparation / evaluation (reference: utils/data_util.py:8-38)."""
+"""Thin callers of the operators used by data preparation / evaluation (reference: utils/data_util.py:8-38), and the label-to-mask
+conversions of the supervised trainer (:64-137)."""
 import torch
 
 from ..pointnet2.pointnet2 import furthest_point_sample, three_interpolate, three_nn
@@ -33,6 +34,48 @@ def segm_to_mask(segm, max_n_object=None):
     if max_n_object is None:
         max_n_object = object_ids.shape[0]
     return np.eye(max_n_object, dtype=np.float32)[inverse]
+
+
+def _sample_mask(segm, max_n_object, ignore_npoint_thresh):
+    """One sample of batch_segm_to_mask: (mask (N, K), valid (N,), the ids kept or None).  Points of objects smaller than the
+    threshold get label 0 IN PLACE (the caller's array changes, as in the reference) and a zero row in the mask."""
+    import numpy as np
+    kept = None
+    if ignore_npoint_thresh > 0:
+        object_ids, object_sizes = np.unique(segm, return_counts=True)
+        kept = object_ids[object_sizes >= ignore_npoint_thresh]
+        valid = np.isin(segm, kept)
+        segm[~valid] = 0
+    else:
+        valid = np.ones_like(segm)
+    valid = valid.astype(np.float32)
+    # ranks of the (possibly relabelled) ids; more than max_n_object of them is an IndexError, as in the reference
+    mask = np.eye(max_n_object, dtype=np.float32)[np.unique(segm, return_inverse=True)[1]]
+    return mask * valid[:, None], valid, kept
+
+
+def batch_segm_to_mask(segms, max_n_object, ignore_npoint_thresh=0):
+    """(B, N) integer labels -> one-hot masks (B, N, max_n_object) float32 over the RANKS of each sample's ids, and valids
+    (B, N) float32: 0 for the points of objects with fewer than ignore_npoint_thresh points (their label is set to 0 in
+    `segms` itself and their mask row is zero).  Reference: data_util.py:64-96."""
+    import numpy as np
+    parts = [_sample_mask(segms[b], max_n_object, ignore_npoint_thresh)[:2] for b in range(segms.shape[0])]
+    return np.stack([m for m, _ in parts], 0), np.stack([v for _, v in parts], 0)
+
+
+def batch_segm_to_mask_withconf(segms, confs, max_n_object, ignore_npoint_thresh=0):
+    """As batch_segm_to_mask, with the mask's leading columns scaled by per-object confidences: confs[b] is (K_b,), indexed
+    by object id when small objects are dropped (conf[ids kept]), and column j < len(conf) is multiplied by conf[j].
+    Reference: data_util.py:99-137."""
+    import numpy as np
+    masks, valids = [], []
+    for b in range(segms.shape[0]):
+        mask, valid, kept = _sample_mask(segms[b], max_n_object, ignore_npoint_thresh)
+        conf = confs[b] if kept is None else confs[b][kept]
+        mask[:, :conf.shape[0]] = mask[:, :conf.shape[0]] * conf[None]
+        masks.append(mask)
+        valids.append(valid)
+    return np.stack(masks, 0), np.stack(valids, 0)
 
 
 def augment_transform(pcs, flows, aug_transform_args, n_view=2, rng=None):

@@ -387,3 +387,29 @@ def write_kitti_downsampled_root(full_root, down_root, n_points, predflow=None, 
     with open(mapping, "w") as f:
         f.write("\n".join(ids) + "\n")
     return mapping, ids
+
+
+SUPERVISED_LAYOUTS = ("sapien", "ogcdr", "kittisf", "kittidet")
+
+
+def write_supervised_roots(root, dataset, n_train, n_val, n_points, n_objects, seed=7000):
+    """A labelled training and a validation set for the supervised trainer (train_seg_sup.py), each under its own directory
+    (the writers number their scenes from 0): <root>/train and <root>/val in the layout `dataset`'s reader takes — kittisf and
+    kittidet by write_labelled_root, ogcdr by write_ogcdr_root, sapien by write_sapien_root.  n_objects counts the moving
+    objects; the four-frame layouts add a background.  Returns {split: (data root, path of the split file or None)}."""
+    import os
+    if dataset not in SUPERVISED_LAYOUTS:
+        raise KeyError("write_supervised_roots covers %s, got %r" % (", ".join(SUPERVISED_LAYOUTS), dataset))
+    out = {}
+    for split, n_scenes, s in (("train", n_train, seed), ("val", n_val, seed + 100003)):
+        sub = os.path.join(root, split)
+        os.makedirs(sub, exist_ok=True)
+        mapping = None
+        if dataset in ("kittisf", "kittidet"):
+            mapping, _ = write_labelled_root(sub, dataset, n_scenes, n_points, n_objects, seed=s, split=split)
+        elif dataset == "ogcdr":
+            write_ogcdr_root(sub, n_scenes, n_points, n_objects=n_objects, seed=s, split=split)
+        else:
+            write_sapien_root(sub, n_scenes, n_points, n_parts=n_objects, seed=s, split=split)
+        out[split] = (sub, mapping)
+    return out
