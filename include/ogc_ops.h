@@ -51,7 +51,7 @@ enum {
  * 0.2.7: ogc_ground_plane_fit.
  * 0.2.8: ogc_seg_eval.  ogc_flow_eval added under 0.2.8: no prototype changed, and the number is pinned by a test of that release.
  * The supervised mask loss (ogc_sup_loss_ws_doubles, ogc_sup_match_cost, ogc_sup_mask_loss_fwd / _bwd) likewise: new entry points
- * only, and two tests of 0.2.8 pin the number. */
+ * only, and two tests of 0.2.8 pin the number.  ogc_seg_eval_ignore likewise: a new entry point, ogc_seg_eval unchanged. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -287,6 +287,27 @@ int ogc_ground_plane_fit(int B, int n, const float *pc, int n_iter, int n_lpr, d
 int ogc_seg_eval(int B, int n, int k, const int *segm, const float *mask, int ignore_npoint_thresh, int *hard, int *counts,
                  double *pred_iou, double *confidence, int *valid, int *n_gt, float *score, int *rows, double *ri, int *status,
                  ogc_stream_t stream);
+
+/* ogc_seg_eval with a per-point ignore mask: ignore (B,n) i32, non-zero = the point is ignored.  The reference ships no such
+ * metric (its test_seg_waymo.py imports a module that is not in its tree); THIS PACKAGE DEFINES IT from the code the reference
+ * does have: an ignored point is a point of a GT object below ignore_npoint_thresh.  The results are what the reference's
+ * eval_segm / ClusteringMetrics give with threshold max(thresh, 2) on the sample in which every ignored point carries a fresh
+ * label of its own (an object of one point); see DESIGN.md 4h for the conditions under which thresh = 0 is covered and the
+ * CPU check of the definition.  Differences from ogc_seg_eval, everything else being computed from these as there:
+ *   - the label of an ignored point is never read (it may be anything; only non-ignored points can set a status bit);
+ *   - hard is written for every point; counts (B,64,k) holds the non-ignored points only; ignored (B,k) i32 is the number of
+ *     ignored points of every slot;
+ *   - the size of a GT object, also for the comparison with thresh, is its number of non-ignored points; n_gt, rows and the
+ *     largest label come from the non-ignored points;
+ *   - the size of a slot is sum_g counts + ignored, its ignored area ignored + the points of dropped objects;
+ *   - the Rand index runs over non-ignored points of objects that are not dropped;
+ *   - confidence is unchanged: the sum runs over every point of the source slot, ignored ones included, over its full size.
+ * A sample whose points are all ignored has n_gt = rows = 0, every valid 0 and ri NaN.  With an all-zero ignore every output
+ * has the bits of ogc_seg_eval's.  Same launch shape, argument checks (ignore and ignored must not be null either) and
+ * run-to-run bit equality. */
+int ogc_seg_eval_ignore(int B, int n, int k, const int *segm, const float *mask, const int *ignore, int ignore_npoint_thresh,
+                        int *hard, int *counts, int *ignored, double *pred_iou, double *confidence, int *valid, int *n_gt,
+                        float *score, int *rows, double *ri, int *status, ogc_stream_t stream);
 
 /* Scene-flow metrics of a batch in one launch (metrics/flow_metric.py:16-24).  gt_flow, flow_pred (B,N,3) f32, contiguous.
  * Per point, in fp32 with one rounding per operation: d = pred - gt, e = sqrtf((dx*dx + dy*dy) + dz*dz), s the same on gt,

@@ -68,6 +68,7 @@ SIGNATURES = {
     "ogc_rigid_icp": [_int, _int, _vp, _vp, _vp, _int, _dbl, _vp, _vp, _vp, _vp],
     "ogc_ground_plane_fit": [_int, _int, _vp, _int, _int, _dbl, _dbl, _int, _vp, _vp, _vp, _vp],
     "ogc_seg_eval": [_int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_seg_eval_ignore": [_int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_flow_eval": [_int, _int, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp],
     "ogc_lsap_maximize": [_int, _int, _vp, _vp, _vp],
     "ogc_sup_loss_ws_doubles": [_int, _int, _int],

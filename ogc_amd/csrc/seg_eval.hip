@@ -18,6 +18,11 @@
 // A sample that holds a label outside [0, OGC_SEG_EVAL_MAX_LABELS) only sets its status bits in pass 1 (nothing is indexed with
 // such a label) and has every other output zeroed; the decision is one LDS word read by all threads after a barrier.
 // Private arrays are not indexed at run time: per-label and per-slot values live in LDS.
+//
+// ogc_seg_eval_ignore is the same kernel with the template parameter IGN: a point whose `ignore` word is non-zero is
+// counted in ign[slot] instead of the table and its label is never read; per slot psize = sum_g tab + ign and the ignored area
+// is ign + the dropped rows' points.  Everything after pass 1 follows from those two numbers as before, and the confidence pass
+// still sums over every point of the source slot.  With IGN = false nothing of this is compiled in.
 #include <math.h>
 
 #include "ogc_common.h"
@@ -36,6 +41,7 @@ struct SegEvalShared {
     int psize[SE_L];                   // points of slot p
     int kept[SE_L];                    // psize minus the points inside ignored (= dropped, non-empty) GT objects
     int source[SE_L];                  // the slot whose points column c is averaged over
+    int ign[SE_L];                     // IGN: points of slot p that the caller's mask ignores (they are in no row of tab)
     unsigned char keep[SE_L];          // label present and not ignored
     unsigned char dropped[SE_L];       // thresh > 0 and size < thresh: the row leaves the clustering table
     int status;
@@ -81,10 +87,12 @@ __device__ __forceinline__ int se_argmax(const float *__restrict__ row, int k) {
     return at;
 }
 
-template <bool VEC4>
+template <bool VEC4, bool IGN>
 __global__ __launch_bounds__(SE_THREADS) void seg_eval_kernel(int n, int k, int thresh, const int *__restrict__ segm_all,
-                                                              const float *__restrict__ mask_all, int *hard_all,
-                                                              int *__restrict__ counts_all, double *__restrict__ pred_iou_all,
+                                                              const float *__restrict__ mask_all,
+                                                              const int *__restrict__ ignore_all, int *hard_all,
+                                                              int *__restrict__ counts_all, int *__restrict__ ignored_all,
+                                                              double *__restrict__ pred_iou_all,
                                                               double *__restrict__ confidence_all, int *__restrict__ valid_all,
                                                               int *__restrict__ n_gt_all, float *__restrict__ score_all,
                                                               int *__restrict__ rows_all, double *__restrict__ ri_all,
@@ -101,17 +109,22 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_kernel(int n, int k, int 
     const int cells = SE_L * k;
 
     for (int e = tid; e < cells; e += nt) sh.tab[e] = 0;
+    if (IGN && tid < SE_L) sh.ign[tid] = 0;
     if (tid == 0) sh.status = 0;
     __syncthreads();
 
     // pass 1
     for (int i = tid; i < n; i += nt) {
         const int at = se_argmax<VEC4>(mask + (size_t)i * k, k);
+        hard[i] = at;
+        if (IGN && ignore_all[b * n + i] != 0) {
+            atomicAdd(&sh.ign[at], 1); // the label of an ignored point is not read
+            continue;
+        }
         const int g = segm[i];
         if (g < 0) atomicOr(&sh.status, 2);
         else if (g >= SE_L) atomicOr(&sh.status, 1);
         else atomicAdd(&sh.tab[g * k + at], 1);
-        hard[i] = at;
     }
     __syncthreads();
 
@@ -124,6 +137,7 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_kernel(int n, int k, int 
             pred_iou_all[b * k + tid] = 0.0;
             confidence_all[b * k + tid] = 0.0;
             valid_all[b * k + tid] = 0;
+            if (IGN) ignored_all[b * k + tid] = 0;
         }
         if (tid == 0) {
             n_gt_all[b] = 0;
@@ -171,6 +185,12 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_kernel(int n, int k, int 
                 ps += m;
                 if (sh.dropped[g]) ignored += m; // empty rows add nothing: dropped and ignored rows hold the same points
                 else m2 += (long long)m * m;
+            }
+            if (IGN) {
+                const int ig = sh.ign[tid];
+                ps += ig;
+                ignored += ig;
+                ignored_all[b * k + tid] = ig;
             }
         }
         const int kept = ps - ignored;
@@ -246,27 +266,44 @@ __global__ __launch_bounds__(SE_THREADS) void seg_eval_kernel(int n, int k, int 
     }
 }
 
+// the argument checks and the launch of both entry points; `ignore` and `ignored` are null exactly when IGN is false
+template <bool IGN>
+int seg_eval_launch(const char *name, int B, int n, int k, const int *segm, const float *mask, const int *ignore,
+                    int ignore_npoint_thresh, int *hard, int *counts, int *ignored, double *pred_iou, double *confidence,
+                    int *valid, int *n_gt, float *score, int *rows, double *ri, int *status, ogc_stream_t stream) {
+    OGC_REQUIRE(B >= 0, "%s: negative batch", name);
+    if (B == 0) return OGC_OK;
+    OGC_REQUIRE(n >= 1, "%s: n = %d, need at least one point per sample", name, n);
+    OGC_REQUIRE(k >= 1 && k <= OGC_SEG_EVAL_MAX_LABELS, "%s: k = %d, need 1 <= k <= %d slots", name, k, OGC_SEG_EVAL_MAX_LABELS);
+    OGC_REQUIRE(ignore_npoint_thresh >= 0, "%s: ignore_npoint_thresh = %d is negative", name, ignore_npoint_thresh);
+    OGC_REQUIRE(segm && mask && hard && counts && pred_iou && confidence && valid && n_gt && score && rows && ri && status,
+                "%s: null pointer", name);
+    OGC_REQUIRE(!IGN || (ignore && ignored), "%s: null pointer (ignore / ignored)", name);
+    const int threads = min(SE_THREADS, ogc_divup(n, OGC_WAVE) * OGC_WAVE);
+    const bool vec4 = (k & 3) == 0 && ((uintptr_t)mask & 15) == 0; // every row starts on a 16-byte boundary
+#define OGC_SEG_EVAL_LAUNCH(VEC4)                                                                                                \
+    hipLaunchKernelGGL((seg_eval_kernel<VEC4, IGN>), dim3(B), dim3(threads), 0, (hipStream_t)stream, n, k, ignore_npoint_thresh, \
+                       segm, mask, ignore, hard, counts, ignored, pred_iou, confidence, valid, n_gt, score, rows, ri, status)
+    if (vec4) OGC_SEG_EVAL_LAUNCH(true);
+    else OGC_SEG_EVAL_LAUNCH(false);
+#undef OGC_SEG_EVAL_LAUNCH
+    OGC_CHECK_LAUNCH(name);
+    return OGC_OK;
+}
+
 } // namespace
 
 extern "C" int ogc_seg_eval(int B, int n, int k, const int *segm, const float *mask, int ignore_npoint_thresh, int *hard,
                             int *counts, double *pred_iou, double *confidence, int *valid, int *n_gt, float *score, int *rows,
                             double *ri, int *status, ogc_stream_t stream) {
-    OGC_REQUIRE(B >= 0, "ogc_seg_eval: negative batch");
-    if (B == 0) return OGC_OK;
-    OGC_REQUIRE(n >= 1, "ogc_seg_eval: n = %d, need at least one point per sample", n);
-    OGC_REQUIRE(k >= 1 && k <= OGC_SEG_EVAL_MAX_LABELS, "ogc_seg_eval: k = %d, need 1 <= k <= %d slots", k,
-                OGC_SEG_EVAL_MAX_LABELS);
-    OGC_REQUIRE(ignore_npoint_thresh >= 0, "ogc_seg_eval: ignore_npoint_thresh = %d is negative", ignore_npoint_thresh);
-    OGC_REQUIRE(segm && mask && hard && counts && pred_iou && confidence && valid && n_gt && score && rows && ri && status,
-                "ogc_seg_eval: null pointer");
-    const int threads = min(SE_THREADS, ogc_divup(n, OGC_WAVE) * OGC_WAVE);
-    const bool vec4 = (k & 3) == 0 && ((uintptr_t)mask & 15) == 0; // every row starts on a 16-byte boundary
-#define OGC_SEG_EVAL_LAUNCH(VEC4)                                                                                                \
-    hipLaunchKernelGGL(seg_eval_kernel<VEC4>, dim3(B), dim3(threads), 0, (hipStream_t)stream, n, k, ignore_npoint_thresh, segm,  \
-                       mask, hard, counts, pred_iou, confidence, valid, n_gt, score, rows, ri, status)
-    if (vec4) OGC_SEG_EVAL_LAUNCH(true);
-    else OGC_SEG_EVAL_LAUNCH(false);
-#undef OGC_SEG_EVAL_LAUNCH
-    OGC_CHECK_LAUNCH("ogc_seg_eval");
-    return OGC_OK;
+    return seg_eval_launch<false>("ogc_seg_eval", B, n, k, segm, mask, nullptr, ignore_npoint_thresh, hard, counts, nullptr,
+                                  pred_iou, confidence, valid, n_gt, score, rows, ri, status, stream);
+}
+
+extern "C" int ogc_seg_eval_ignore(int B, int n, int k, const int *segm, const float *mask, const int *ignore,
+                                   int ignore_npoint_thresh, int *hard, int *counts, int *ignored, double *pred_iou,
+                                   double *confidence, int *valid, int *n_gt, float *score, int *rows, double *ri, int *status,
+                                   ogc_stream_t stream) {
+    return seg_eval_launch<true>("ogc_seg_eval_ignore", B, n, k, segm, mask, ignore, ignore_npoint_thresh, hard, counts, ignored,
+                                 pred_iou, confidence, valid, n_gt, score, rows, ri, status, stream);
 }

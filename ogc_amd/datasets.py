@@ -18,6 +18,11 @@ one directory tree:
                              <root>/flow_preds/<name>/<sequence>/flow_%04d_%04d.npy.  A sample id is (sequence, t, t - 1); with
                              downsampled=False the four items are lists of two frames with their own numbers of points
 
+  WaymoSingleFrameDataset    the same files without the flows, one frame per sample: a sample id is (sequence, t)
+                             (datasets/dataset_waymo_singleframe.py:54-206), and a sample is (pcs, segms, valids) — no flows.
+                             For the supervised Waymo baseline and the Waymo evaluation (train_seg_waymo_sup.py,
+                             test_seg_waymo.py); predicted segmentations <save_root>/<sequence>/segm_%04d.npy
+
   KITTIDetectionDataset      <root>/downsampled/<id>/{pc,segm}.npy, a split file listing the ids (datasets/dataset_kittidet.py)
   SemanticKITTIDataset       the same files; the ids are the sorted directory names whose first two characters are a sequence
                              number in `sequence_list` (datasets/dataset_semantickitti.py).  Both are single-frame sets for
@@ -237,6 +242,87 @@ class WaymoOpenDataset(Dataset):
             d = os.path.join(save_root, name)
             os.makedirs(d, exist_ok=True)
             np.save(os.path.join(d, "flow_%04d_%04d.npy" % (view1, view2)), flow_pred[i])
+
+
+class WaymoSingleFrameDataset(WaymoOpenDataset):
+    """Reference: datasets/dataset_waymo_singleframe.py:54-206 (its class is also called WaymoOpenDataset).  One frame per
+    sample, id (sequence, t); a sample is (pcs (1, N, 3) f32, segms (1, N) i32, valids (1, N) i32) with the ignored points —
+    semantic classes `ignore_class_ids`, objects below `ignore_npoint_thresh` — at label 0 and valid 0.  With `onehot_label`
+    segms is (1, N, max_n_object) f32, one-hot over the ranks of the filtered labels times valid, and valids is f32.  With
+    `aug_transform` the frame is doubled for the augmentation and views 0 and 2 — the two transforms of the one frame — come
+    back as pcs (2, N, 3), while segms and valids are repeated to two entries: the reference's shapes, kept.  With
+    downsampled=False the three items are one-element lists as loaded."""
+
+    def __init__(self, data_root, mapping_path, downsampled=False, select_frame=None, sampled_interval=1, decentralize=False,
+                 aug_transform=False, aug_transform_args=None, onehot_label=False, max_n_object=20, ignore_class_ids=(),
+                 ignore_npoint_thresh=0):
+        import json
+        self.data_root = os.path.join(data_root, "data")
+        with open(mapping_path, "r") as f:
+            self.sequence_list = [line.strip() for line in f if line.strip()]
+        self.downsampled = downsampled
+        if select_frame is not None:
+            with open(select_frame, "r") as f:
+                self.data_ids = [(str(seq), int(t)) for seq, t in json.load(f)]
+        else:
+            self.data_ids = self._make_dataset(sampled_interval)
+        self.decentralize = decentralize
+        self.aug_transform, self.aug_transform_args = aug_transform, aug_transform_args
+        self.onehot_label, self.max_n_object = onehot_label, max_n_object
+        self.ignore_class_ids, self.ignore_npoint_thresh = list(ignore_class_ids), ignore_npoint_thresh
+
+    def _make_dataset(self, sampled_interval):
+        """Every frame of every listed sequence that is on disk (`n_skipped` counts the others)."""
+        import glob
+        data_ids, self.n_skipped = [], 0
+        for entry in self.sequence_list:
+            name = os.path.splitext(entry)[0]
+            d = os.path.join(self.data_root, name)
+            if not os.path.exists(d):
+                self.n_skipped += 1
+                continue
+            data_ids += [(name, t) for t in range(len(glob.glob(os.path.join(d, "pc_*"))))]
+        return data_ids[::sampled_interval] if sampled_interval > 1 else data_ids
+
+    def _load_data(self, name, view):
+        d = os.path.join(self.data_root, name)
+        return tuple([np.load(os.path.join(d, "%s_%04d.npy" % (what, view)))] for what in ("pc", "segm", "semantic_segm"))
+
+    def __getitem__(self, sid):
+        name, view = self.data_ids[sid]
+        pcs, segms, semantic_segms = self._load_data(name, view)
+        segms, valids = self.filter_segm(segms, semantic_segms)
+        if not self.downsampled:
+            return pcs, segms, valids
+        pcs, segms, valids = np.stack(pcs, 0), np.stack(segms, 0), np.stack(valids, 0)
+        if self.decentralize:
+            pcs = pcs - pcs.mean(1).mean(0)
+        segms = np.stack([compress_label_id(segm) for segm in segms], 0)
+        if self.onehot_label:
+            assert self.max_n_object > 0, 'max_n_object must be above 0!'
+            segms = np.eye(self.max_n_object, dtype=np.float32)[segms] * np.expand_dims(valids, 2)
+        if self.aug_transform:       # the frame as both frames of a pair with zero flows; views 0 and 2 are its two transforms
+            pcs = np.concatenate((pcs, pcs), 0)
+            pcs, _ = augment_transform(pcs, np.zeros_like(pcs), self.aug_transform_args)
+            pcs = pcs[[0, 2]]
+            segms, valids = np.concatenate((segms, segms), 0), np.concatenate((valids, valids), 0)
+        if self.onehot_label:
+            return pcs.astype(np.float32), segms.astype(np.float32), valids.astype(np.float32)
+        return pcs.astype(np.float32), segms.astype(np.int32), valids.astype(np.int32)
+
+    def _load_flow(self, name, view1, view2):
+        raise NotImplementedError("the single-frame reader has no flows")
+
+    _load_predflow = _save_predflow = _load_flow
+
+    def _save_predsegm(self, mask_or_hard, save_root, batch_size, n_frame=1, offset=0):
+        """(B, N, K) masks or (B, N) hard labels -> <save_root>/<sequence>/segm_%04d.npy, int64; sample `offset * batch_size + i`
+        (dataset_waymo_singleframe.py:194-206, which does not divide by n_frame)."""
+        hard = _hard_labels(mask_or_hard)
+        for i in range(hard.shape[0]):
+            name, view = self.data_ids[offset * batch_size + i]
+            os.makedirs(os.path.join(save_root, name), exist_ok=True)
+            np.save(os.path.join(save_root, name, "segm_%04d.npy" % view), hard[i])
 
 
 def compute_flow(pc1, segm1, pose1, pose2):

@@ -390,6 +390,16 @@ def seg_eval_wrapper(b, n, k, segm, mask, ignore_npoint_thresh, hard, counts, pr
          _i(status, "status"))
 
 
+def seg_eval_ignore_wrapper(b, n, k, segm, mask, ignore, ignore_npoint_thresh, hard, counts, ignored, pred_iou, confidence, valid,
+                            n_gt, score, rows, ri, status):
+    """seg_eval_wrapper with a per-point ignore mask (ogc_seg_eval_ignore): ignore (b, n) i32, non-zero = ignored; one more output,
+    ignored (b, k) i32, the ignored points of every slot.  counts holds the non-ignored points only."""
+    _run("ogc_seg_eval_ignore", mask, b, n, k, _i(segm, "segm"), _f(mask, "mask"), _i(ignore, "ignore"), int(ignore_npoint_thresh),
+         _i(hard, "hard"), _i(counts, "counts"), _i(ignored, "ignored"), _check(pred_iou, torch.float64, "pred_iou"),
+         _check(confidence, torch.float64, "confidence"), _i(valid, "valid"), _i(n_gt, "n_gt"), _f(score, "score"),
+         _i(rows, "rows"), _check(ri, torch.float64, "ri"), _i(status, "status"))
+
+
 def flow_eval_wrapper(b, n, gt_flow, flow_pred, epe_norm_thresh, eps, epe_sum, counts):
     """Scene-flow metrics of b samples in one launch (ogc_flow_eval): gt_flow, flow_pred (b, n, 3) f32 -> epe_sum (b,) f64 the
     sum of the end-point errors, counts (b, 3) i32 the strict-accurate, relaxed-accurate and outlier points."""

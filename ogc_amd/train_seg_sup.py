@@ -16,7 +16,8 @@ What differs from the reference is invisible in the numbers: the optimiser step 
 device, no host round trip), the loss does not synchronise (sync=False), and the monitored PQ / F1 / Pre / Rec of every
 iteration and epoch come from metrics.seg_eval — one ogc_seg_eval launch and one small copy — where the reference copies the
 full soft masks to the host every iteration.  `_train_it` therefore returns device tensors.  No tensorboard: one JSON line per
-epoch.  Out of scope: train_seg_waymo_sup.py, data-parallel training, HIP-graph replay.
+epoch.  The Waymo baseline (train_seg_waymo_sup.py) is ogc_amd/train_seg_waymo_sup.py, a subclass of this Trainer on batches
+without flows.  Out of scope: data-parallel training, HIP-graph replay.
 """
 import argparse
 import json

@@ -215,6 +215,47 @@ def write_waymo_root(root, n_sequences, n_frames, n_points, seed=2000, split="va
     return mapping, poses
 
 
+def write_waymo_singleframe_roots(root, n_train, n_val, n_frames, n_points, seed=8000, small_object=20):
+    """Single-frame Waymo data for the supervised Waymo trainer and the Waymo evaluation (WaymoSingleFrameDataset with
+    downsampled=True): sequences of make_waymo_sequence under <root>/data/<split>_%04d/{pc,segm,semantic_segm}_%04d.npy, every
+    frame cut to exactly `n_points` points so that frames batch, with what makes the reader's ignore mask non-empty whatever the
+    threshold: box 4 is of class 2 (make_waymo_sequence's), box 2 becomes class 3, and `small_object` points of box 1 in every
+    frame become an object of their own (id n_boxes + 1, class 1) that a threshold above `small_object` drops.
+    Writes <root>/train.txt and <root>/val.txt (one name listed in each is not on disk: the readers pass over it) and
+    <root>/train_select.json / val_select.json with every second frame as [sequence, t].
+    Returns {"train": {"mapping", "select_frame", "names"}, "val": {...}}."""
+    import json
+    import os
+
+    import numpy as np
+    out, k = {}, 0
+    os.makedirs(root, exist_ok=True)
+    for split, n_sequences in (("train", n_train), ("val", n_val)):
+        names = []
+        for _ in range(n_sequences):
+            name = "%s_%04d" % (split, len(names))
+            frames = make_waymo_sequence(n_frames, n_points + n_points // 19 + 2, seed=seed + k)   # n - 5 % >= n_points
+            k += 1
+            d = os.path.join(root, "data", name)
+            os.makedirs(d, exist_ok=True)
+            for t, frame in enumerate(frames):
+                pc, segm, semantic = (frame[what][:n_points].copy() for what in ("pc", "segm", "semantic_segm"))
+                assert pc.shape[0] == n_points
+                semantic[segm == 2] = 3
+                fragment = np.nonzero(segm == 1)[0][:small_object]
+                segm[fragment] = int(frame["segm"].max()) + 1
+                for what, value in (("pc", pc), ("segm", segm), ("semantic_segm", semantic)):
+                    np.save(os.path.join(d, "%s_%04d.npy" % (what, t)), value)
+            names.append(name)
+        mapping, select = os.path.join(root, split + ".txt"), os.path.join(root, split + "_select.json")
+        with open(mapping, "w") as f:
+            f.write("\n".join(["%s.tfrecord" % n for n in names] + ["%s_absent.tfrecord" % split]) + "\n")
+        with open(select, "w") as f:
+            json.dump([[n, t] for n in names for t in range(0, n_frames, 2)], f)
+        out[split] = {"mapping": mapping, "select_frame": select, "names": names}
+    return out
+
+
 LABELLED_LAYOUTS = ("kittisf", "kittidet", "semantickitti")
 SYNTHETIC_SEQUENCES = (0, 8, 12)   # synthetic frames cycle through these; test_seg evaluates sequences 0..10
 
