@@ -696,6 +696,7 @@ int ogc_group_norm_maxpool_bwd_ext(int b, int c, int p, int s, int groups, int r
  * gamma, beta, grad_gamma, grad_beta, mean, rstd (c) (mean / rstd written by fwd, read by bwd).
  * stats / slots: optional statistics supplied by the producing kernel (`slots` copies of a (c, 2) f64 accumulator), else
  * NULL / 0 and ws (2c f64) is used.  bwd ws: 3c f64.
+ * All four: b <= 65535 and c * hw (c * p * s) < 2^31, OGC_ERR_INVALID_ARG otherwise, nothing launched.
  * training == 0 with mean == rstd == NULL (inference, nothing kept for a backward pass): the affine map is formed from the
  * running statistics inside the apply kernel itself — one launch. */
 int ogc_batch_norm_fwd(int b, int c, int hw, float eps, int relu, int training, float momentum, const float *x,

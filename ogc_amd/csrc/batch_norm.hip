@@ -514,6 +514,8 @@ extern "C" int ogc_batch_norm_bwd(int b, int c, int hw, int relu, int training, 
                                   ogc_stream_t stream) {
     OGC_REQUIRE(b >= 0 && c >= 1 && hw >= 1, "ogc_batch_norm_bwd: bad shape");
     if (b == 0) return OGC_OK;
+    // before the pointers are looked at: b is a grid dimension, c * hw the span of the kernels' int offsets
+    OGC_REQUIRE((long long)c * hw < (1ll << 31) && b <= 65535, "ogc_batch_norm_bwd: one sample exceeds 32-bit indexing");
     OGC_REQUIRE(x && gamma && beta && mean && rstd && grad_y && grad_x && grad_gamma && grad_beta && ws,
                 "ogc_batch_norm_bwd: null pointer");
     hipStream_t s = (hipStream_t)stream;
@@ -600,6 +602,8 @@ extern "C" int ogc_batch_norm_maxpool_bwd(int b, int c, int p, int s, int relu, 
         return OGC_ERR_UNSUPPORTED;
     }
     if (b == 0) return OGC_OK;
+    OGC_REQUIRE((long long)c * p * s < (1ll << 31) && b <= 65535,
+                "ogc_batch_norm_maxpool_bwd: one sample exceeds 32-bit indexing");
     OGC_REQUIRE(x && gamma && mean && rstd && out && argmax && grad_out && grad_x && grad_gamma && grad_beta && ws,
                 "ogc_batch_norm_maxpool_bwd: null pointer");
     hipStream_t st = (hipStream_t)stream;

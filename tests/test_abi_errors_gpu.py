@@ -39,6 +39,12 @@ for name, argtypes in sorted(_lib.SIGNATURES.items()):
     msg = L.ogc_last_error().decode("utf-8", "replace")
     torch.cuda.synchronize()
     print("RESULT %s %d %d %s" % (name, rc_empty, rc_null, msg.replace("\n", " ")), flush=True)
+# shapes beyond the kernels' indexing (a batch that is no grid dimension, a sample past 2^31 elements): refused as such BEFORE the
+# buffers are looked at — they are all missing, so a call that got as far as the pointer check says "null pointer" instead
+for name, ints in (("ogc_batch_norm_bwd", (65536, 1, 4, 1, 1)), ("ogc_batch_norm_bwd", (1, 65536, 32768, 1, 1)),
+                   ("ogc_batch_norm_maxpool_bwd", (65536, 1, 4, 4, 1, 1)), ("ogc_batch_norm_maxpool_bwd", (1, 65536, 8192, 4, 1, 1))):
+    rc = getattr(L, name)(*(list(ints) + [None] * (len(_lib.SIGNATURES[name]) - len(ints) - 1) + [stream]))
+    print("RANGE %s %d %s" % (name, rc, L.ogc_last_error().decode("utf-8", "replace").replace("\n", " ")), flush=True)
 print("DONE", flush=True)
 '''
 
@@ -57,3 +63,7 @@ def test_every_entry_point_refuses_null_buffers_and_accepts_empty_batches():
         # first integer zero (the batch for most entry points): a no-op or an argument refusal, never a failed launch
         assert int(rc_empty) in (0, -1, -3), "%s: status %s with a zero leading dimension" % (name, rc_empty)
         assert int(rc_null) in (-1, -3), "%s: status %s for null buffers" % (name, rc_null)
+    ranged = [l.split(" ", 3) for l in out.stdout.splitlines() if l.startswith("RANGE ")]
+    assert [l[1] for l in ranged] == ["ogc_batch_norm_bwd"] * 2 + ["ogc_batch_norm_maxpool_bwd"] * 2
+    for _, name, rc, msg in ranged:
+        assert int(rc) == -1 and "32-bit indexing" in msg, "%s: status %s (%s) for a shape beyond 32-bit indexing" % (name, rc, msg)
