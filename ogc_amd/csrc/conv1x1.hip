@@ -493,6 +493,13 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE, DUAL ? 2 : 1) void conv1x1_gemm
     if (STATS) flush_stats();
 }
 
+// dynamic LDS of the streaming kernel: the weights | PRO: [wave][2][FW_KQ_MAX * 4] | [wave][4 * 16][2] doubles | POOL: [Mt * 64] signs
+size_t gemm_stream_lds(int M, int K, bool pro, bool pool) {
+    const int Kq = (K + 3) / 4, Mt = (M + 63) / 64;
+    return ((size_t)Mt * 64 * ogc_a_ld(Kq) + (pro ? WG_WAVES * 2 * FW_KQ_MAX * 4 : 0)) * sizeof(float) +
+           WG_WAVES * 4 * 16 * 2 * sizeof(double) + (pool ? (size_t)Mt * 64 * sizeof(float) : 0);
+}
+
 // the streaming kernel for this shape, or false when the tile kernel should run
 // shapes the streaming kernel takes (fp32 operands only)
 // (pool: the launch also carries the sign strip of the pooled epilogue — one float per staged row)
@@ -500,45 +507,28 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE, DUAL ? 2 : 1) void conv1x1_gemm
 // `matmul_precision: bf16` too — the alternative there is the bf16 tile kernel followed by a statistics pass of its own, and for
 // a pooled tail the dense backward path)
 bool gemm_stream_eligible(int b, int M, int K, int hw, bool pro, bool pool = false, bool any_precision = false) {
-    const int Kq = (K + 3) / 4, Mt = (M + 63) / 64;
+    const int Kq = (K + 3) / 4;
     const long long ntiles = (long long)b * (hw / 64);
-    const size_t lds = ((size_t)Mt * 64 * ogc_a_ld(Kq) + (pro ? WG_WAVES * 2 * FW_KQ_MAX * 4 : 0)) * sizeof(float) +
-                       WG_WAVES * 4 * 16 * 2 * sizeof(double) + (pool ? (size_t)Mt * 64 * sizeof(float) : 0);
     static const bool off = getenv("OGC_GEMM_STREAM") && getenv("OGC_GEMM_STREAM")[0] == '0';
-    return !(off || (g_matmul_bf16 && !any_precision) || (hw & 63) != 0 || Kq <= 25 || Kq > FW_KQ_MAX || lds > 156 * 1024 || ntiles < 2048 ||
-             ntiles >= (1ll << 31));
+    return !(off || (g_matmul_bf16 && !any_precision) || (hw & 63) != 0 || Kq <= 25 || Kq > FW_KQ_MAX ||
+             gemm_stream_lds(M, K, pro, pool) > 156 * 1024 || ntiles < 2048 || ntiles >= (1ll << 31));
 }
 
 template <bool PRO, bool STATS = false, bool POOL = false, bool TRANS = false>
 bool gemm_stream_launch(int b, int M, int K, int hw, const float *w, const float *in, float *out, const float *pa,
                         const float *pb, int pro_relu, hipStream_t s, int groups = 1, double *stats = nullptr,
                         PoolOut pool = PoolOut()) {
-    const int Kq = (K + 3) / 4, Mt = (M + 63) / 64;
+    const int Kq = (K + 3) / 4;
     const long long ntiles = (long long)b * (hw / 64);
-    const size_t lds = ((size_t)Mt * 64 * ogc_a_ld(Kq) + (PRO ? WG_WAVES * 2 * FW_KQ_MAX * 4 : 0)) * sizeof(float) +
-                       WG_WAVES * 4 * 16 * 2 * sizeof(double) + (POOL ? (size_t)Mt * 64 * sizeof(float) : 0);
-    if (!gemm_stream_eligible(b, M, K, hw, PRO, POOL, STATS) || lds > 156 * 1024) return false;
-    const int wgs = (int)(ntiles / WG_WAVES < 256 ? ntiles / WG_WAVES : 256);
-#define OGC_STREAM_D(KQV, EX, DU, WGS)                                                                                       \
-    do {                                                                                                                     \
-        static bool raised = false;                                                                                          \
-        const void *fn = reinterpret_cast<const void *>(&conv1x1_gemm_stream_kernel<KQV, PRO, EX, STATS, POOL, DU, TRANS>);         \
-        if (!raised) {                                                                                                       \
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return false;  \
-            raised = true;                                                                                                   \
-        }                                                                                                                    \
-        hipLaunchKernelGGL((conv1x1_gemm_stream_kernel<KQV, PRO, EX, STATS, POOL, DU, TRANS>), dim3(WGS), dim3(WG_WAVES * OGC_WAVE), \
-                           lds, s, M, K, hw, (int)ntiles, w, in, out, pa, pb, pro_relu, groups, b, stats, pool);             \
-    } while (0)
+    const size_t lds = gemm_stream_lds(M, K, PRO, POOL);
+    if (!gemm_stream_eligible(b, M, K, hw, PRO, POOL, STATS)) return false;
     // two workgroups per CU where the weights of both fit the LDS (the 128-channel layers; OGC_GEMM_STREAM_DUAL=0: one)
     static const bool dual_on = !(getenv("OGC_GEMM_STREAM_DUAL") && getenv("OGC_GEMM_STREAM_DUAL")[0] == '0');
     const bool dual = dual_on && !POOL && 2 * (lds + 1024) <= 156 * 1024 && ntiles >= 4096;
-    const int wgs2 = (int)(ntiles / WG_WAVES < 512 ? ntiles / WG_WAVES : 512);
-#define OGC_STREAM(KQV, EX)                                                                                                  \
-    do {                                                                                                                     \
-        if (dual) OGC_STREAM_D(KQV, EX, true, wgs2);                                                                         \
-        else OGC_STREAM_D(KQV, EX, false, wgs);                                                                              \
-    } while (0)
+#define OGC_STREAM_D(KQV, EX, DU)                                                                                            \
+    ogc_persistent_launch<&conv1x1_gemm_stream_kernel<KQV, PRO, EX, STATS, POOL, DU, TRANS>>(                                \
+        lds, 156 * 1024, DU ? 2 : 1, ntiles, s, M, K, hw, (int)ntiles, w, in, out, pa, pb, pro_relu, groups, b, stats, pool)
+#define OGC_STREAM(KQV, EX) return dual ? OGC_STREAM_D(KQV, EX, true) : OGC_STREAM_D(KQV, EX, false)
     const bool full_rows = M % 64 == 0;
     if (Kq == 32 && full_rows) OGC_STREAM(32, true);         // K = 125 .. 128 (the 128-channel layers)
     else if (Kq == 33 && full_rows) OGC_STREAM(33, true);    // K = 129 .. 132 (131: 128 features + 3 coordinates)
@@ -546,7 +536,6 @@ bool gemm_stream_launch(int b, int M, int K, int hw, const float *w, const float
     else OGC_STREAM(40, false);
 #undef OGC_STREAM
 #undef OGC_STREAM_D
-    return true;
 }
 
 template <bool T, bool STATS, bool PRO, bool POOL = false, typename AT = float>

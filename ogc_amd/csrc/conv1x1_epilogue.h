@@ -1,6 +1,7 @@
-// conv1x1_epilogue.h — what the forward / input-gradient GEMM kernels of conv1x1.hip (register tile per wavefront, fp32 or 16-bit
-// tensors) and conv1x1_h.hip (persistent kernel for 16-bit tensors) share: constants, the pooled epilogue (PoolOut, see "POOL" at
-// conv1x1_gemm_kernel) and its one-instruction maxima.
+// conv1x1_epilogue.h — what the four forward / input-gradient GEMM kernels share: conv1x1_gemm_kernel and conv1x1_gemm_stream_kernel
+// (conv1x1.hip: a register tile per wavefront; persistent, fp32, K > 100) and conv1x1_gemm16_kernel and conv1x1_gemm32_kernel
+// (conv1x1_h.hip: persistent, 16-bit tensors; persistent, fp32, K <= 64): constants, the pooled epilogue (PoolOut, see "POOL" at
+// conv1x1_gemm_kernel) and its one-instruction maxima, and, on the host, the launch of a persistent kernel.
 #pragma once
 #include "conv1x1_shared.h"
 
@@ -84,15 +85,24 @@ __device__ __forceinline__ void ogc_pool_extremes_epilogue(const ACC (&acc)[4][4
     }
 }
 
+// ---- host: the launch of a persistent kernel ------------------------------------------------------------------------------------------
+// KERNEL with `lds` bytes of dynamic LDS on min(256 per_cu, ntiles / 4) workgroups of four wavefronts (256 CUs).  The limit on
+// dynamic LDS is raised to lds_cap once per kernel instantiation (one `raised` per KERNEL); false, with the error cleared, when
+// the runtime refuses.
+template <auto KERNEL, typename... ARGS>
+bool ogc_persistent_launch(size_t lds, int lds_cap, int per_cu, long long ntiles, hipStream_t s, ARGS... args) {
+    static bool raised = false;
+    if (!raised) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        raised = true;
+    }
+    long long wgs = 256ll * per_cu;
+    if (wgs > ntiles / WG_WAVES) wgs = ntiles / WG_WAVES;
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)wgs), dim3(WG_WAVES * OGC_WAVE), lds, s, args...);
+    return true;
+}
 
 } // namespace
-
-// (conv1x1_h.hip) the persistent kernel for 16-bit tensors; false when the shape is not its (the caller launches the tile kernel)
-bool ogc_gemm16_launch(bool transpose_a, bool stats_on, bool pro, bool pool_on, int b, int M, int K, int hw, int groups,
-                       const float *w, const unsigned short *in, unsigned short *out, double *stats, const float *pa,
-                       const float *pb, int pro_relu, hipStream_t s, const float *pool_sign, float *pool_yext, int *pool_aext,
-                       int pool_s);
-// (conv1x1_h.hip) the persistent kernel for fp32 tensors with <= 64 reduction channels; false when the shape is not its
-bool ogc_gemm32_launch(bool transpose_a, bool stats_on, bool pro, bool pool_on, int b, int M, int K, int hw, int groups,
-                       const float *w, const float *in, float *out, double *stats, const float *pa, const float *pb, int pro_relu,
-                       hipStream_t s, const float *pool_sign, float *pool_yext, int *pool_aext, int pool_s);

@@ -478,76 +478,60 @@ __global__ __launch_bounds__(H_WAVES *OGC_WAVE, OCC) void conv1x1_gemm32_kernel(
     if (STATS) flush_stats();
 }
 
-template <bool TRANS, int KQ, bool STATS, bool PRO, bool POOL, int OCC>
-bool gemm32_go(int b, int M, int K, int hw, int groups, const float *w, const float *in, float *out, double *stats, const float *pa,
-               const float *pb, int pro_relu, hipStream_t s, PoolOut pool) {
+// ---- host ----------------------------------------------------------------------------------------------------------------------------
+// dynamic LDS of the two kernels (their layouts: the "LDS:" comments in the kernels)
+size_t gemm32_lds(int M, int K, int KQ, bool stats_on, bool pro, bool pool_on) {
     const int Kq = (K + 3) / 4, Mt = (M + 63) / 64;
-    const size_t lds = ((size_t)Mt * 64 * ogc_a_ld(Kq) + (PRO ? H_WAVES * 2 * KQ * 4 : 0) + (STATS ? H_WAVES * Mt * 64 : 0) +
-                        (POOL ? Mt * 64 : 0)) * sizeof(float);
-    const long long ntiles = (long long)b * (hw / 64);
-    int per_cu = OCC;
-    while (per_cu > 1 && (lds + 512) * per_cu > 156 * 1024) --per_cu;
-    if (lds > 78 * 1024 || ntiles >= (1ll << 31)) return false;
-    static bool raised = false;
-    const void *fn = reinterpret_cast<const void *>(&conv1x1_gemm32_kernel<TRANS, KQ, STATS, PRO, POOL, OCC>);
-    if (!raised) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 78 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        raised = true;
-    }
-    long long wgs = 256ll * per_cu;
-    if (wgs > ntiles / H_WAVES) wgs = ntiles / H_WAVES;
-    hipLaunchKernelGGL((conv1x1_gemm32_kernel<TRANS, KQ, STATS, PRO, POOL, OCC>), dim3((unsigned)wgs), dim3(H_WAVES * OGC_WAVE), lds, s, M,
-                       K, hw, (int)ntiles, b, groups, w, in, out, stats, pa, pb, pro_relu, pool);
-    return true;
+    return ((size_t)Mt * 64 * ogc_a_ld(Kq) + (pro ? H_WAVES * 2 * KQ * 4 : 0) + (stats_on ? H_WAVES * Mt * 64 : 0) +
+            (pool_on ? Mt * 64 : 0)) * sizeof(float);
 }
-
-template <bool TRANS, bool STATS, bool PRO, bool POOL>
-bool gemm32_kq(int b, int M, int K, int hw, int groups, const float *w, const float *in, float *out, double *stats, const float *pa,
-               const float *pb, int pro_relu, hipStream_t s, PoolOut pool) {
-    const int Kq = (K + 3) / 4;
-    if (Kq <= 8) return gemm32_go<TRANS, 8, STATS, PRO, POOL, 2>(b, M, K, hw, groups, w, in, out, stats, pa, pb, pro_relu, s, pool);
-    if (Kq <= 16) return gemm32_go<TRANS, 16, STATS, PRO, POOL, 2>(b, M, K, hw, groups, w, in, out, stats, pa, pb, pro_relu, s, pool);
-    return false;
-}
-
 size_t gemm16_lds(int M, int K, int KQ, bool stats_on, bool pro, bool pool_on, bool adj = false) {
     const int Kq = (K + 3) / 4, Gq = (Kq + 3) / 4, Mt = (M + 63) / 64;
     return ((size_t)Mt * Gq * 512 + (pro ? H_WAVES * 2 * KQ * 4 : 0) + (stats_on ? H_WAVES * Mt * 64 : 0) + (pool_on ? Mt * 64 : 0) +
             (adj ? H_WAVES * Mt * 64 * 5 : 0)) * sizeof(float);
 }
 
-template <bool TRANS, int KQ, bool STATS, bool PRO, bool POOL, bool PF, int OCC, bool RAG, bool ADJ = false>
-bool gemm16_go(int b, int M, int K, int hw, int groups, const float *w, const ogc_bf16 *in, ogc_bf16 *out, double *stats,
-               const float *pa, const float *pb, int pro_relu, hipStream_t s, PoolOut pool, AdjIn adj = AdjIn()) {
-    const size_t lds = gemm16_lds(M, K, KQ, STATS, PRO, POOL, ADJ);
-    const long long ntiles = (long long)b * (hw / 64);
+// KERNEL (built for OCC wavefronts per SIMD) on this call, or false: its LDS beyond 78 KiB, too many tiles for 32-bit counters
+template <auto KERNEL, int OCC, typename... ARGS>
+bool h_go(size_t lds, long long ntiles, hipStream_t s, ARGS... args) {
     int per_cu = OCC; // workgroups per CU: what the registers allow, and the LDS (160 KiB per CU)
     while (per_cu > 1 && (lds + 512) * per_cu > 156 * 1024) --per_cu;
     if (lds > 78 * 1024 || ntiles >= (1ll << 31)) return false;
-    static bool raised = false;
-    const void *fn = reinterpret_cast<const void *>(&conv1x1_gemm16_kernel<TRANS, KQ, STATS, PRO, POOL, PF, OCC, RAG, ADJ>);
-    if (!raised) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 78 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        raised = true;
-    }
-    long long wgs = 256ll * per_cu;
-    if (wgs > ntiles / H_WAVES) wgs = ntiles / H_WAVES;
-    hipLaunchKernelGGL((conv1x1_gemm16_kernel<TRANS, KQ, STATS, PRO, POOL, PF, OCC, RAG, ADJ>), dim3((unsigned)wgs), dim3(H_WAVES * OGC_WAVE), lds,
-                       s, M, K, hw, (int)ntiles, b, groups, w, in, out, stats, pa, pb, pro_relu, pool, adj);
-    return true;
+    return ogc_persistent_launch<KERNEL>(lds, 78 * 1024, per_cu, ntiles, s, args...);
+}
+
+template <bool TRANS, int KQ, bool STATS, bool PRO, bool POOL, int OCC>
+bool gemm32_go(int b, int M, int K, int hw, int groups, const float *w, const float *in, float *out, double *stats, const float *pa,
+               const float *pb, int pro_relu, hipStream_t s, PoolOut pool) {
+    const long long ntiles = (long long)b * (hw / 64);
+    return h_go<&conv1x1_gemm32_kernel<TRANS, KQ, STATS, PRO, POOL, OCC>, OCC>(
+        gemm32_lds(M, K, KQ, STATS, PRO, POOL), ntiles, s, M, K, hw, (int)ntiles, b, groups, w, in, out, stats, pa, pb, pro_relu, pool);
+}
+
+template <bool TRANS, int KQ, bool STATS, bool PRO, bool POOL, bool PF, int OCC, bool RAG, bool ADJ = false>
+bool gemm16_go(int b, int M, int K, int hw, int groups, const float *w, const ogc_bf16 *in, ogc_bf16 *out, double *stats,
+               const float *pa, const float *pb, int pro_relu, hipStream_t s, PoolOut pool, AdjIn adj = AdjIn()) {
+    const long long ntiles = (long long)b * (hw / 64);
+    return h_go<&conv1x1_gemm16_kernel<TRANS, KQ, STATS, PRO, POOL, PF, OCC, RAG, ADJ>, OCC>(
+        gemm16_lds(M, K, KQ, STATS, PRO, POOL, ADJ), ntiles, s, M, K, hw, (int)ntiles, b, groups, w, in, out, stats, pa, pb, pro_relu, pool,
+        adj);
+}
+
+// the kernel instantiation for K reduction channels: overloads on the tensors' element type
+#define H_ARGS b, M, K, hw, groups, w, in, out, stats, pa, pb, pro_relu, s, pool
+template <bool TRANS, bool STATS, bool PRO, bool POOL>
+bool h_kq(int b, int M, int K, int hw, int groups, const float *w, const float *in, float *out, double *stats, const float *pa,
+          const float *pb, int pro_relu, hipStream_t s, PoolOut pool) {
+    const int Kq = (K + 3) / 4;
+    if (Kq <= 8) return gemm32_go<TRANS, 8, STATS, PRO, POOL, 2>(H_ARGS);
+    if (Kq <= 16) return gemm32_go<TRANS, 16, STATS, PRO, POOL, 2>(H_ARGS);
+    return false;
 }
 
 template <bool TRANS, bool STATS, bool PRO, bool POOL>
-bool gemm16_kq(int b, int M, int K, int hw, int groups, const float *w, const ogc_bf16 *in, ogc_bf16 *out, double *stats,
-               const float *pa, const float *pb, int pro_relu, hipStream_t s, PoolOut pool) {
+bool h_kq(int b, int M, int K, int hw, int groups, const float *w, const ogc_bf16 *in, ogc_bf16 *out, double *stats,
+          const float *pa, const float *pb, int pro_relu, hipStream_t s, PoolOut pool) {
     const int Kq = (K + 3) / 4;
-#define H_ARGS b, M, K, hw, groups, w, in, out, stats, pa, pb, pro_relu, s, pool
     // two wavefronts per SIMD either way (three, built without the prefetch, spill at K <= 64); the prefetched tile does not fit the
     // registers next to 33 quads of operands
     const bool exact = (K & 3) == 0;
@@ -557,9 +541,33 @@ bool gemm16_kq(int b, int M, int K, int hw, int groups, const float *w, const og
     }
     if (exact && Kq == 32) return gemm16_go<TRANS, 32, STATS, PRO, POOL, false, 2, false>(H_ARGS);
     if (Kq <= 33) return gemm16_go<TRANS, 33, STATS, PRO, POOL, false, 2, true>(H_ARGS);
-#undef H_ARGS
     return false;
 }
+
+// The (TRANS, STATS, PRO, POOL) forms the persistent kernels are built in: the plain input gradient; the pooled tail with statistics
+// and folded norm; forward with and without either — statistics without the folded norm for fp32 tensors only.
+template <typename AT>
+bool h_dispatch(bool transpose_a, bool stats_on, bool pro, bool pool_on, int b, int M, int K, int hw, int groups, const float *w,
+                const AT *in, AT *out, double *stats, const float *pa, const float *pb, int pro_relu, hipStream_t s, PoolOut pool) {
+#define H_GO(T, ST, PR, PO) return h_kq<T, ST, PR, PO>(H_ARGS)
+    if (transpose_a) {
+        if (!stats_on && !pro && !pool_on) H_GO(true, false, false, false);
+        return false;
+    }
+    if (pool_on) {
+        if (stats_on && pro) H_GO(false, true, true, true);
+        return false;
+    }
+    if (stats_on && pro) H_GO(false, true, true, false);
+    if constexpr (sizeof(AT) == 4) {
+        if (stats_on && !pro) H_GO(false, true, false, false);
+    }
+    if (!stats_on && pro) H_GO(false, false, true, false);
+    if (!stats_on && !pro) H_GO(false, false, false, false);
+#undef H_GO
+    return false;
+}
+#undef H_ARGS
 
 } // namespace
 
@@ -572,22 +580,8 @@ bool ogc_gemm16_launch(bool transpose_a, bool stats_on, bool pro, bool pool_on, 
     const char *e = getenv("OGC_GEMM16"); // (read per call: tests flip it)
     if (e && e[0] == '0') return false;
     if ((hw & 63) != 0 || (long long)b * (hw / 64) < 8192) return false;
-    PoolOut pool;
-    pool.yext = pool_yext; pool.aext = pool_aext; pool.sign = pool_sign; pool.s = pool_s;
-#define H_GO(T, ST, PR, PO) return gemm16_kq<T, ST, PR, PO>(b, M, K, hw, groups, w, in, out, stats, pa, pb, pro_relu, s, pool)
-    if (transpose_a) {
-        if (!stats_on && !pro && !pool_on) H_GO(true, false, false, false);
-        return false;
-    }
-    if (pool_on) {
-        if (stats_on && pro) H_GO(false, true, true, true);
-        return false;
-    }
-    if (stats_on && pro) H_GO(false, true, true, false);
-    if (!stats_on && pro) H_GO(false, false, true, false);
-    if (!stats_on && !pro) H_GO(false, false, false, false);
-#undef H_GO
-    return false;
+    return h_dispatch(transpose_a, stats_on, pro, pool_on, b, M, K, hw, groups, w, in, out, stats, pa, pb, pro_relu, s,
+                      PoolOut{pool_yext, pool_aext, pool_sign, pool_s});
 }
 
 // The adjoint input gradient (ogc_conv1x1_dgrad_adjoint_h, dense form) on the persistent kernel, or false (fewer than 8192 position
@@ -620,21 +614,6 @@ bool ogc_gemm32_launch(bool transpose_a, bool stats_on, bool pro, bool pool_on, 
     // against 0.134, pooled 64 -> 128: 0.292 against 0.270 (tools/gemm32_bench.py).  OGC_GEMM32=all: every K <= 64 (tests).
     const bool all = e && e[0] == 'a';
     if ((hw & 63) != 0 || (long long)b * (hw / 64) < 8192 || K > 64 || (K <= 32 && !all)) return false;
-    PoolOut pool;
-    pool.yext = pool_yext; pool.aext = pool_aext; pool.sign = pool_sign; pool.s = pool_s;
-#define H_GO(T, ST, PR, PO) return gemm32_kq<T, ST, PR, PO>(b, M, K, hw, groups, w, in, out, stats, pa, pb, pro_relu, s, pool)
-    if (transpose_a) {
-        if (!stats_on && !pro && !pool_on) H_GO(true, false, false, false);
-        return false;
-    }
-    if (pool_on) {
-        if (stats_on && pro) H_GO(false, true, true, true);
-        return false;
-    }
-    if (stats_on && pro) H_GO(false, true, true, false);
-    if (stats_on && !pro) H_GO(false, true, false, false);
-    if (!stats_on && pro) H_GO(false, false, true, false);
-    if (!stats_on && !pro) H_GO(false, false, false, false);
-#undef H_GO
-    return false;
+    return h_dispatch(transpose_a, stats_on, pro, pool_on, b, M, K, hw, groups, w, in, out, stats, pa, pb, pro_relu, s,
+                      PoolOut{pool_yext, pool_aext, pool_sign, pool_s});
 }

@@ -11,6 +11,20 @@
 
 __host__ __device__ __forceinline__ int ogc_a_ld(int Kq) { return 4 * (Kq | 1); }
 
+// The launchers of the persistent kernels of conv1x1_h.hip, for conv1x1.hip and gn_fused_bwd.hip; false: not the kernel's shape (the
+// caller launches its own kernel).  16-bit tensors; fp32 tensors with <= 64 reduction channels; the dense adjoint input gradient
+// for 16-bit tensors.
+bool ogc_gemm16_launch(bool transpose_a, bool stats_on, bool pro, bool pool_on, int b, int M, int K, int hw, int groups,
+                       const float *w, const unsigned short *in, unsigned short *out, double *stats, const float *pa,
+                       const float *pb, int pro_relu, hipStream_t s, const float *pool_sign, float *pool_yext, int *pool_aext,
+                       int pool_s);
+bool ogc_gemm32_launch(bool transpose_a, bool stats_on, bool pro, bool pool_on, int b, int M, int K, int hw, int groups,
+                       const float *w, const float *in, float *out, double *stats, const float *pa, const float *pb, int pro_relu,
+                       hipStream_t s, const float *pool_sign, float *pool_yext, int *pool_aext, int pool_s);
+bool ogc_gemm16_adjoint_launch(int b, int M, int K, int hw, int relu, const float *w, const unsigned short *gy,
+                               const unsigned short *yprev, const float *pa, const float *pb, const float *coef,
+                               unsigned short *out, hipStream_t s);
+
 template <bool TRANSPOSE, int WAVES>
 __device__ __forceinline__ void ogc_stage_weight_tile(float *__restrict__ a_lds, const float *__restrict__ w, int m0, int M,
                                                       int K, int Kq) {

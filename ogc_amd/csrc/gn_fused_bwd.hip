@@ -26,10 +26,6 @@
 #include "act_io.h"
 
 extern int ogc_g_matmul_bf16; // (conv1x1.hip) operand precision switch
-// (conv1x1_h.hip) the dense adjoint input gradient for 16-bit tensors on the persistent kernel; false: not its shape
-bool ogc_gemm16_adjoint_launch(int b, int M, int K, int hw, int relu, const float *w, const unsigned short *gy,
-                               const unsigned short *yprev, const float *pa, const float *pb, const float *coef,
-                               unsigned short *out, hipStream_t s);
 
 namespace {
 

@@ -1239,13 +1239,58 @@ def test_folded_inference_weights_follow_training(nat):
     torch.testing.assert_close(second, second_ref, rtol=1e-4, atol=1e-5)
 
 
-@pytest.mark.parametrize("B,cin,cout,hw,relu", [(4, 128, 128, 32768, 1), (3, 131, 256, 45056, 1), (8, 128, 64, 16384, 0)])
-def test_conv1x1_gemm_affine_streaming_kernel(nat, B, cin, cout, hw, relu):
+# one process = one setting of OGC_GEMM_STREAM (the library reads it once): the three calls on seeded inputs, outputs to argv[6]
+_STREAM_DUMP = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, %r)
+import ogc_amd
+from ogc_amd import pointnet2_cuda as nat
+B, cin, cout, hw, relu = (int(a) for a in sys.argv[1:6])
+g = torch.Generator().manual_seed(cin + cout)
+w = (torch.randn(cout, cin, generator=g) * 0.3).cuda()
+x = torch.randn(B, cin, hw, generator=g).cuda()
+pa = (torch.rand(B, cin, generator=g) + 0.5).cuda()
+pb = (torch.randn(B, cin, generator=g) * 0.5).cuda()
+y = torch.full((B, cout, hw), float("nan"), device="cuda")
+nat.conv1x1_gemm_affine_wrapper(B, cout, cin, hw, relu, 0, w, x, pa, pb, y, None)
+np.save(sys.argv[6] + ".affine.npy", y.cpu().numpy())
+y.fill_(float("nan"))
+nat.conv1x1_gemm_wrapper(B, cout, cin, hw, 0, w, x, y)
+np.save(sys.argv[6] + ".plain.npy", y.cpu().numpy())
+y.fill_(float("nan"))
+nat.conv1x1_gemm_wrapper(B, cout, cin, hw, 1, w.t().contiguous(), x, y)   # A = w^T, w stored (K, M)
+np.save(sys.argv[6] + ".trans.npy", y.cpu().numpy())
+"""
+
+
+@pytest.mark.parametrize("B,cin,cout,hw,relu", [(4, 128, 128, 32768, 1), (3, 131, 256, 45056, 1), (8, 128, 64, 16384, 0),
+                                                # the smallest shapes that reach each instantiation of the streaming kernel:
+                                                (2, 128, 128, 65536, 1),   # KQ 32 exact, 2048 tiles
+                                                (4, 128, 128, 65536, 1),   # 4096 tiles (two workgroups per CU where the LDS admits it)
+                                                (2, 131, 64, 65536, 1),    # KQ 33 exact
+                                                (2, 104, 96, 65536, 1),    # KQ 33, ragged K quads, M no multiple of 64
+                                                (2, 160, 128, 65536, 1)])  # KQ 40
+def test_conv1x1_gemm_affine_streaming_kernel(nat, tmp_path, B, cin, cout, hw, relu):
     """ogc_conv1x1_gemm_affine at shapes that take the streaming kernel (K > 100, >= 2048 position tiles): out = W act(pa x + pb)
-    against float64; and the same call with the streaming kernel switched off must give the same bits (same FMA chains)."""
-    import os
+    against float64; and the same call with the streaming kernel switched off (OGC_GEMM_STREAM=0: the tile kernel) must give the
+    same bits (same FMA chains), as must ogc_conv1x1_gemm in both orientations.  (Statistics and pooling at K > 100 have no
+    tile-kernel form under fp32 operands.)"""
     import subprocess
     import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / "dump.py"
+    script.write_text(_STREAM_DUMP % root)
+    env = {k: v for k, v in os.environ.items() if k != "OGC_GEMM_STREAM"}
+    outs = {"on": str(tmp_path / "on"), "off": str(tmp_path / "off")}
+    for mode in ("on", "off"):                           # one after the other, each under its own timeout
+        subprocess.run([sys.executable, str(script)] + [str(a) for a in (B, cin, cout, hw, relu)] + [outs[mode]], check=True,
+                       timeout=300, env=dict(env, OGC_GEMM_STREAM="0") if mode == "off" else env)
+    for call in ("affine", "plain", "trans"):
+        on, off = np.load(outs["on"] + ".%s.npy" % call), np.load(outs["off"] + ".%s.npy" % call)
+        assert np.isfinite(on).all(), call
+        assert np.array_equal(on, off), (call, float(np.abs(on - off).max()))
+    del on, off
+
     torch.manual_seed(cin + cout)
     w = torch.randn(cout, cin, device=DEV) * 0.3
     x = torch.randn(B, cin, hw, device=DEV)
