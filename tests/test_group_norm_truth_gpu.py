@@ -267,7 +267,7 @@ def host_extremes(d):
 @pytest.mark.parametrize("slots", gc.STATS_SLOTS)
 def test_supplied_statistics(nat, slots):
     """fwd_stats, coeffs, maxpool_fwd_stats and pool_extremes on float64 partial sums made on the host, `slots` of them: the slot
-    loop of gn_sum_slots with counts that are no multiple of 8, one more than 8, and the most the library writes."""
+    loop of gn_mean_rstd with counts that are no multiple of 8, one more than 8, and the most the library writes."""
     c = gc.STATS_PLAIN
     d = gc.make(c)
     ref, B, C, G, hw = gc.reference(c, d, DEV), c.B, c.C, c.groups, c.dims[0]
