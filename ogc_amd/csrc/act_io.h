@@ -17,6 +17,13 @@ __device__ __forceinline__ float4 ogc_ld4(const ogc_bf16 *p) {
     return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16),
                        __uint_as_float(u.y & 0xFFFF0000u));
 }
+// eight consecutive bf16 values, as loaded in one 16-byte piece, widened
+__device__ __forceinline__ void ogc_unpack8(const uint4 &u, float (&f)[8]) {
+    f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xFFFF0000u);
+    f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xFFFF0000u);
+    f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xFFFF0000u);
+    f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xFFFF0000u);
+}
 __device__ __forceinline__ float ogc_ld1(const float *p) { return *p; }
 __device__ __forceinline__ float ogc_ld1(const ogc_bf16 *p) { return __uint_as_float((unsigned)*p << 16); }
 

@@ -19,6 +19,42 @@ constexpr int WG_WAVES = 4;
 extern int ogc_g_matmul_bf16;
 #define g_matmul_bf16 ogc_g_matmul_bf16
 
+// ---- the two maps the weight-gradient kernels apply to what they load, over N = 4 or 8 consecutive positions of one row ------------
+// The gradient behind a pooled GroupNorm, rebuilt from the convolution's raw output y (ogc_group_norm_maxpool_bwd_sparse):
+//     g_y[row, pos] = fmaf(c2, y, c3) + (pos % S == arg ? ag : 0)        (c2, c3) = coef2[b, row], (ag, arg) = jv = inj[b, row, pos / S]
+// — the expression of gn_maxpool_bwd_dx_kernel, bit for bit.  jpos: position of v[0] inside its neighbourhood (the N positions
+// lie inside one neighbourhood: S >= 16); arg travels as int bits.
+template <int N>
+__device__ __forceinline__ void ogc_pooled_grad(float (&v)[N], float c2, float c3, const float2 &jv, int jpos) {
+    const int rel = __float_as_int(jv.y) - jpos;
+    const float ag = jv.x;
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = fmaf(c2, v[e], c3) + (rel == e ? ag : 0.f);
+}
+template <int N>
+__device__ __forceinline__ void ogc_affine_act(float (&v)[N], float a, float b, int relu) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        v[e] = fmaf(a, v[e], b);
+        if (relu) v[e] = fmaxf(v[e], 0.f);
+    }
+}
+// The same two on a float4 = four consecutive positions.  Spelled on the components: through a float[4] (and with the ReLU
+// as a second loop) the array forms moved the register allocation of 55 of the 134 weight-gradient kernels.
+__device__ __forceinline__ void ogc_pooled_grad(float4 &v, float c2, float c3, const float2 &jv, int jpos) {
+    const int rel = __float_as_int(jv.y) - jpos;
+    const float ag = jv.x;
+    v.x = fmaf(c2, v.x, c3) + (rel == 0 ? ag : 0.f);
+    v.y = fmaf(c2, v.y, c3) + (rel == 1 ? ag : 0.f);
+    v.z = fmaf(c2, v.z, c3) + (rel == 2 ? ag : 0.f);
+    v.w = fmaf(c2, v.w, c3) + (rel == 3 ? ag : 0.f);
+}
+__device__ __forceinline__ void ogc_affine_act(float4 &v, float a, float b, int relu) {
+    v.x = fmaf(a, v.x, b); v.y = fmaf(a, v.y, b);
+    v.z = fmaf(a, v.z, b); v.w = fmaf(a, v.w, b);
+    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+}
+
 __device__ __forceinline__ v4s ogc_pack_bf16(float a, float b, float c, float d) {
     typedef float v2f __attribute__((ext_vector_type(2)));
     typedef __bf16 v2bf __attribute__((ext_vector_type(2)));

@@ -21,16 +21,10 @@
 //   ogc_conv1x1_wgrad_moments   H, H2          (v_mfma_f32_16x16x4_f32, two accumulator sets)
 //   ogc_gn_moments_combine      dW, dgamma, dbeta, and alpha / c2 / c3 per (sample, channel)
 //   ogc_conv1x1_dgrad_adjoint   g_prev
-#include "ogc_common.h"
-#include "conv_stage.h"
+#include "conv1x1_shared.h" // v4f, WG_WAVES, ogc_pooled_grad, the operand precision switch ogc_g_matmul_bf16 (conv1x1.hip)
 #include "act_io.h"
 
-extern int ogc_g_matmul_bf16; // (conv1x1.hip) operand precision switch
-
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-constexpr int WG_WAVES = 4;
 
 // ---- moment matrices ------------------------------------------------------------------------------------------------
 // Same operand layout as conv1x1_wgrad_kernel: for a step of 16 positions lane (i = l & 15, k = l >> 4) loads ONE float4 =
@@ -114,14 +108,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
     auto fma16 = [&](float4(&yv)[COB], const float4(&xraw)[CIB], const float2(&jv)[COB], int jpos) {
         if (POOLED) {
 #pragma unroll
-            for (int a = 0; a < COB; ++a) { // the expression of gn_maxpool_bwd_dx_kernel, bit for bit
-                const int rel = __float_as_int(jv[a].y) - jpos;
-                const float ag = jv[a].x;
-                yv[a].x = fmaf(pc2[a], yv[a].x, pc3[a]) + (rel == 0 ? ag : 0.f);
-                yv[a].y = fmaf(pc2[a], yv[a].y, pc3[a]) + (rel == 1 ? ag : 0.f);
-                yv[a].z = fmaf(pc2[a], yv[a].z, pc3[a]) + (rel == 2 ? ag : 0.f);
-                yv[a].w = fmaf(pc2[a], yv[a].w, pc3[a]) + (rel == 3 ? ag : 0.f);
-            }
+            for (int a = 0; a < COB; ++a) ogc_pooled_grad(yv[a], pc2[a], pc3[a], jv[a], jpos); // (gn_maxpool_bwd_dx_kernel's expression)
         }
         float4 m1[CIB], m2[CIB];
 #pragma unroll
@@ -193,13 +180,6 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
 // Nothing is rounded that was not already: dy (dense form) is used as loaded, the mask is 0 / 1, mask . x is x or 0; only the
 // POOLED form rebuilds g_y in fp32 and rounds it (bf16 operands, as everywhere under ogc_set_matmul_precision(1)).
 typedef short v4s16 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void ogc_unpack8(const uint4 &u, float (&f)[8]) {
-    f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xFFFF0000u);
-    f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xFFFF0000u);
-    f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xFFFF0000u);
-    f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xFFFF0000u);
-}
 
 template <int COB, int CIB, bool POOLED>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments16_kernel(int cin, int cout, int hw, int chunks,
@@ -276,10 +256,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments16_kernel(int
             if (POOLED) { // the expression of gn_maxpool_bwd_dx_kernel on the stored y, rounded to the operand precision
                 float f[8];
                 ogc_unpack8(yraw[a], f);
-                const int rel = __float_as_int(jv[a].y) - jpos;
-                const float ag = jv[a].x;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = fmaf(pc2[a], f[e], pc3[a]) + (rel == e ? ag : 0.f);
+                ogc_pooled_grad(f, pc2[a], pc3[a], jv[a], jpos);
                 y0[a] = ogc_pack_bf16_rr(f[0], f[1], f[2], f[3]);
                 y1[a] = ogc_pack_bf16_rr(f[4], f[5], f[6], f[7]);
             } else {
