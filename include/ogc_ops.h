@@ -51,7 +51,8 @@ enum {
  * 0.2.7: ogc_ground_plane_fit.
  * 0.2.8: ogc_seg_eval.  ogc_flow_eval added under 0.2.8: no prototype changed, and the number is pinned by a test of that release.
  * The supervised mask loss (ogc_sup_loss_ws_doubles, ogc_sup_match_cost, ogc_sup_mask_loss_fwd / _bwd) likewise: new entry points
- * only, and two tests of 0.2.8 pin the number.  ogc_seg_eval_ignore likewise: a new entry point, ogc_seg_eval unchanged. */
+ * only, and two tests of 0.2.8 pin the number.  ogc_seg_eval_ignore likewise: a new entry point, ogc_seg_eval unchanged.
+ * ogc_soft_carry likewise: a new entry point, no prototype changed. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -538,6 +539,19 @@ int ogc_neighbour_consistency_bwd(int b, int n, int c, int k, int p, const float
  * formula (|a|^2 + |b|^2 - 2 a.b, clamped, sqrt).  k <= 32. */
 int ogc_soft_nn_target(int b, int n1, int n2, int k, float temperature, const float *p1, const float *p2,
                        const float *mask1, const float *mask2, float *target, ogc_stream_t stream);
+
+/* Values carried over a soft correspondence, fused (multi-frame voting).  Replaces
+ *   vote.py:17-28, :52-58:  corr = softmax(-cdist(p1, p2) / temperature);  out = corr @ x
+ * (an (n1, n2) matrix per adjacent frame pair — 268 MB at 8192 points — multiplied into thin matrices) by two passes over the
+ * candidates on the matrix cores: the nearest distance of every query, then the weights against that fixed maximum fed straight
+ * into the second product.  Nothing of size n1 x n2 is stored.
+ *   out[b, m, :] = sum_n softmax_n(-|p1[b,m] - p2[b,n]| / temperature) * x[b, n, :]
+ * p1 (b,n1,3) query points, already warped (pc + flow); p2 (b,n2,3) candidates; x (b,n2,c) values living on the candidates;
+ * out (b,n1,c).  Distances use torch.cdist's large-matrix formula (|a|^2 + |b|^2 - 2 a.b, clamped, sqrt).  1 <= c <= 64
+ * (OGC_ERR_UNSUPPORTED beyond: split x by columns), n2 >= 1, temperature > 0; b == 0 or n1 == 0 is a no-op.  A sample's result
+ * does not depend on the other samples of the call (sums in a fixed order). */
+int ogc_soft_carry(int b, int n1, int n2, int c, float temperature, const float *p1, const float *p2, const float *x,
+                   float *out, ogc_stream_t stream);
 
 /* Attention core of the MaskFormer head's nn.MultiheadAttention layers
  *   utils/transformer_util.py:5-62 (cross-attention slots <- points, self-attention among the slots; 8 heads,

@@ -81,6 +81,7 @@ SIGNATURES = {
     "ogc_mask_iou": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp],
     "ogc_matched_distance": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_soft_nn_target": [_int, _int, _int, _int, _flt, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_soft_carry": [_int, _int, _int, _int, _flt, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_concat": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_fwd": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_bwd": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],

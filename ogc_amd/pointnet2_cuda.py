@@ -454,6 +454,20 @@ def soft_nn_target_wrapper(b, n1, n2, k, temperature, p1, p2, mask1, mask2, targ
          _f(mask2, "mask2"), _f(target, "target"))
 
 
+def soft_carry_wrapper(b, n1, n2, c, temperature, p1, p2, x, out):
+    """out (b, n1, c) = softmax_rows(-cdist(p1, p2) / temperature) @ x without the (b, n1, n2) tensor (ogc_soft_carry).
+    The kernel takes up to 64 columns: wider x goes through in column blocks."""
+    if c <= 64:
+        _run("ogc_soft_carry", p1, b, n1, n2, c, float(temperature), _f(p1, "p1"), _f(p2, "p2"), _f(x, "x"), _f(out, "out"))
+        return
+    _f(x, "x"), _f(out, "out")
+    for c0 in range(0, c, 64):
+        xb = x[:, :, c0:c0 + 64].contiguous()
+        ob = torch.empty(b, n1, xb.shape[2], dtype=torch.float32, device=out.device)
+        _run("ogc_soft_carry", p1, b, n1, n2, xb.shape[2], float(temperature), _f(p1, "p1"), _f(p2, "p2"), _f(xb, "x"), _f(ob, "out"))
+        out[:, :, c0:c0 + 64] = ob
+
+
 def rigid_moments_wrapper(vb, n, k, pc, pc2, mask, mom, S, means):
     """Weighted moments -> centred cross-covariances S and means per (cloud, slot) (ogc_rigid_moments)."""
     _run("ogc_rigid_moments", pc, vb, n, k, _f(pc, "pc"), _f(pc2, "pc2"), _f(mask, "mask"),
