@@ -52,7 +52,8 @@ enum {
  * 0.2.8: ogc_seg_eval.  ogc_flow_eval added under 0.2.8: no prototype changed, and the number is pinned by a test of that release.
  * The supervised mask loss (ogc_sup_loss_ws_doubles, ogc_sup_match_cost, ogc_sup_mask_loss_fwd / _bwd) likewise: new entry points
  * only, and two tests of 0.2.8 pin the number.  ogc_seg_eval_ignore likewise: a new entry point, ogc_seg_eval unchanged.
- * ogc_soft_carry likewise: a new entry point, no prototype changed. */
+ * ogc_soft_carry likewise: a new entry point, no prototype changed.  ogc_scan_crop_camera / _front / _tile and ogc_box_segm /
+ * _chunk likewise. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -552,6 +553,44 @@ int ogc_soft_nn_target(int b, int n1, int n2, int k, float temperature, const fl
  * does not depend on the other samples of the call (sums in a fixed order). */
 int ogc_soft_carry(int b, int n1, int n2, int c, float temperature, const float *p1, const float *p2, const float *x,
                    float *out, ogc_stream_t stream);
+
+/* Data preparation, stage 1: the crop of a raw scan to the front-view cloud, as a STABLE stream compaction.  Replaces
+ *   data_prepare/kittidet/process_kittidet.py:99-114, data_prepare/semantickitti/process_semantickitti.py:61-78   (camera)
+ *   data_prepare/waymo/process_waymo.py:132-141                                                                    (front)
+ * scan (n, stride) f32 with xyz in columns 0..2; out_pc (n, 3) f32, keep_idx (n,) i32, count (1,) i32, all device memory.
+ * Rows 0 .. count-1 of out_pc / keep_idx hold the kept points and their scan rows IN SCAN ORDER (the reference indexes with the
+ * boolean mask, and FPS starts at row 0 and breaks ties by index); rows >= count are not written.  n == 0: OGC_OK, count = 0,
+ * no kernel.  Two launches on `stream` and OGC_SCAN_CROP_TILE points per workgroup; no workgroup waits for another.
+ *
+ * camera: `cam` points to OGC_SCAN_CROP_CAMERA_DOUBLES doubles on the device:
+ *   [0, 12)  V2C, 3 x 4 row-major (Tr_velo_to_cam / Tr)        [12, 21)  R0, 3 x 3 row-major (R0_rect)
+ *   [21, 33) P, 3 x 4 row-major (P2)                           [33] image width   [34] image height
+ *   [35]     0: R0 is skipped (SemanticKITTI has none), otherwise it is applied
+ * Per point p, in fp64, sums left to right, never contracted: ref = V2C [p, 1]; rect = R0 ref (or ref); img = P [rect, 1];
+ * u = img0 / img2, v = img1 / img2; out = fp32(rect * (-1, -1, 1)).  Kept iff u < W && u >= 0 && v < H && v >= 0 &&
+ * p.x > clip_distance (fp32) && out.z < depth_thresh (fp32).  inf / NaN from img2 == 0 fail the comparisons.  stride >= 3.
+ * front: kept iff scan[:, 5] == -1 && x > |y| && (x*x + y*y) + z*z < 3600 && |y| < 50 && x < 35, all fp32 with one rounding per
+ * operation; out is the input xyz.  stride >= 6. */
+#define OGC_SCAN_CROP_TILE 1024
+#define OGC_SCAN_CROP_CAMERA_DOUBLES 36
+int ogc_scan_crop_camera(int n, int stride, const float *scan, const double *cam, float clip_distance, float depth_thresh,
+                         float *out_pc, int *keep_idx, int *count, ogc_stream_t stream);
+int ogc_scan_crop_front(int n, int stride, const float *scan, float *out_pc, int *keep_idx, int *count, ogc_stream_t stream);
+int ogc_scan_crop_tile(void); /* OGC_SCAN_CROP_TILE of the library */
+
+/* Data preparation, stage 2: labels of points from oriented boxes, the LAST box that holds a point wins.  Replaces the box loops
+ *   data_prepare/waymo/process_waymo.py:48-84, data_prepare/kittidet/process_kittidet.py:33-65
+ * pc (n, 3) f32; sign_x / _y / _z in {1, -1}, applied to the point first; boxes (k, OGC_BOX_SEGM_BOX_DOUBLES) f64:
+ *   [0, 9) rot, 3 x 3 row-major    [9, 12) centre c    [12, 15) lo    [15, 18) hi
+ * ids (k, 2) i32: object id, class id.  segm, semantic_segm (n,) i32 out.  Per point and box in fp64, never contracted:
+ *   d = sign * p - c;  q_i = (rot_i0 d_0 + rot_i1 d_1) + rot_i2 d_2;  inside iff lo_i < q_i && q_i < hi_i for i = 0, 1, 2
+ * and the point gets the ids of the highest k whose box holds it, 0 / 0 when none does (k == 0: all zeros).  One thread per
+ * point, the boxes staged in LDS OGC_BOX_SEGM_CHUNK at a time from the last to the first. */
+#define OGC_BOX_SEGM_CHUNK 128
+#define OGC_BOX_SEGM_BOX_DOUBLES 18
+int ogc_box_segm(int n, int k, const float *pc, int sign_x, int sign_y, int sign_z, const double *boxes, const int *ids,
+                 int *segm, int *semantic_segm, ogc_stream_t stream);
+int ogc_box_segm_chunk(void); /* OGC_BOX_SEGM_CHUNK of the library */
 
 /* Attention core of the MaskFormer head's nn.MultiheadAttention layers
  *   utils/transformer_util.py:5-62 (cross-attention slots <- points, self-attention among the slots; 8 heads,

@@ -82,6 +82,11 @@ SIGNATURES = {
     "ogc_matched_distance": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_soft_nn_target": [_int, _int, _int, _int, _flt, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_soft_carry": [_int, _int, _int, _int, _flt, _vp, _vp, _vp, _vp, _vp],
+    "ogc_scan_crop_camera": [_int, _int, _vp, _vp, _flt, _flt, _vp, _vp, _vp, _vp],
+    "ogc_scan_crop_front": [_int, _int, _vp, _vp, _vp, _vp, _vp],
+    "ogc_scan_crop_tile": [],
+    "ogc_box_segm": [_int, _int, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp],
+    "ogc_box_segm_chunk": [],
     "ogc_group_concat": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_fwd": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_bwd": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],

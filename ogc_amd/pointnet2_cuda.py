@@ -407,6 +407,32 @@ def flow_eval_wrapper(b, n, gt_flow, flow_pred, epe_norm_thresh, eps, epe_sum, c
          _check(epe_sum, torch.float64, "epe_sum"), _i(counts, "counts"))
 
 
+SCAN_CROP_TILE = 1024        # OGC_SCAN_CROP_TILE: points per workgroup of the crop kernels
+SCAN_CROP_CAMERA_DOUBLES = 36  # OGC_SCAN_CROP_CAMERA_DOUBLES: V2C (12) | R0 (9) | P (12) | width | height | R0 applied
+BOX_SEGM_CHUNK = 128         # OGC_BOX_SEGM_CHUNK: boxes staged in LDS at a time
+BOX_SEGM_BOX_DOUBLES = 18    # OGC_BOX_SEGM_BOX_DOUBLES: rot (9) | centre (3) | lo (3) | hi (3)
+
+
+def scan_crop_camera_wrapper(n, stride, scan, cam, clip_distance, depth_thresh, out_pc, keep_idx, count):
+    """Camera crop of a raw scan as a stable compaction (ogc_scan_crop_camera): scan (n, stride) f32, cam (36,) f64 -> rows
+    0 .. count-1 of out_pc (n, 3) f32 and keep_idx (n,) i32 in scan order, count (1,) i32; later rows are not written."""
+    _run("ogc_scan_crop_camera", count, n, stride, _f(scan, "scan"), _check(cam, torch.float64, "cam"), float(clip_distance),
+         float(depth_thresh), _f(out_pc, "out_pc"), _i(keep_idx, "keep_idx"), _i(count, "count"))
+
+
+def scan_crop_front_wrapper(n, stride, scan, out_pc, keep_idx, count):
+    """Front-view crop of an (n, stride >= 6) Waymo scan as a stable compaction (ogc_scan_crop_front); outputs as above."""
+    _run("ogc_scan_crop_front", count, n, stride, _f(scan, "scan"), _f(out_pc, "out_pc"), _i(keep_idx, "keep_idx"),
+         _i(count, "count"))
+
+
+def box_segm_wrapper(n, k, pc, sign, boxes, ids, segm, semantic_segm):
+    """Labels of n points from k oriented boxes, the last box wins (ogc_box_segm): pc (n, 3) f32, sign three ints in {1, -1},
+    boxes (k, 18) f64, ids (k, 2) i32 -> segm, semantic_segm (n,) i32."""
+    _run("ogc_box_segm", segm, n, k, _f(pc, "pc"), int(sign[0]), int(sign[1]), int(sign[2]), _check(boxes, torch.float64, "boxes"),
+         _i(ids, "ids"), _i(segm, "segm"), _i(semantic_segm, "semantic_segm"))
+
+
 def group_concat_wrapper(b, c, n, npoints, nsample, xyz, new_xyz, points, idx, out):
     """out = cat([xyz[idx] - new_xyz, points[idx]], dim=1) (ogc_group_concat); points may be None when c == 0."""
     _run("ogc_group_concat", xyz, b, c, n, npoints, nsample, _f(xyz, "xyz"), _f(new_xyz, "new_xyz"),

@@ -454,3 +454,270 @@ def write_supervised_roots(root, dataset, n_train, n_val, n_points, n_objects, s
             write_sapien_root(sub, n_scenes, n_points, n_parts=n_objects, seed=s, split=split)
         out[split] = (sub, mapping)
     return out
+
+
+# ---- raw roots for the preparation drivers (ogc_amd/data_prepare) ----------------------------------------------------------
+RAW_MARGIN = 0.05            # object points lie this far inside their box, all others this far outside every relaxed box
+RAW_RELAX = 0.01             # the `relax` of the reference's box tests
+KITTI_IMAGE_SIZE = (1242, 375)
+
+
+def _rot_x_np(angle):
+    import numpy as np
+    c, s = np.cos(angle), np.sin(angle)
+    return np.array([[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]])
+
+
+def _rot_z_np(angle):
+    import numpy as np
+    c, s = np.cos(angle), np.sin(angle)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+def _written(values):
+    """What a reader gets back from numbers written with %.12e."""
+    import numpy as np
+    return np.array([float("%.12e" % v) for v in np.asarray(values, dtype=np.float64).reshape(-1)])
+
+
+def make_kitti_calibration(seed, with_r0=True):
+    """A KITTI-like calibration as the numbers a calib file holds: P2 (3, 4) a 721-px pinhole with a baseline term, V2C (3, 4)
+    the velodyne frame (x forward, y left, z up) turned into the camera's (x right, y down, z forward) under a tilt of a degree
+    or so and a lever arm, R0 (3, 3) a rectifying rotation of a few milliradians (None without)."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    axes = np.array([[0.0, -1.0, 0.0], [0.0, 0.0, -1.0], [1.0, 0.0, 0.0]])
+    tilt = _rot_x_np((rs.rand() - 0.5) * 0.03) @ _rot_y_np((rs.rand() - 0.5) * 0.03) @ _rot_z_np((rs.rand() - 0.5) * 0.03)
+    V2C = np.concatenate([tilt @ axes, np.array([[-0.004], [-0.076], [-0.272]]) + (rs.rand(3, 1) - 0.5) * 0.01], 1)
+    P = np.array([[721.5377, 0.0, 609.5593, 44.85728], [0.0, 721.5377, 172.854, 0.2163791], [0.0, 0.0, 1.0, 0.002745884]])
+    calib = {"P": _written(P).reshape(3, 4), "V2C": _written(V2C).reshape(3, 4)}
+    if with_r0:
+        R0 = _rot_x_np((rs.rand() - 0.5) * 0.02) @ _rot_y_np((rs.rand() - 0.5) * 0.02) @ _rot_z_np((rs.rand() - 0.5) * 0.02)
+        calib["R0"] = _written(R0).reshape(3, 3)
+    return calib
+
+
+def _rect_to_velo(rect, calib):
+    """Camera (rect) coordinates -> velodyne coordinates, float64."""
+    import numpy as np
+    ref = rect @ np.linalg.inv(calib["R0"]).T if calib.get("R0") is not None else rect
+    return (ref - calib["V2C"][:, 3]) @ np.linalg.inv(calib["V2C"][:, :3]).T
+
+
+def _camera_scene(n_points, rs, objects):
+    """Points of one camera frame in RECT coordinates (x right, y down, z forward; the camera 1.65 m above the ground) and their
+    object index (0: none).  `objects` is a list of (l, w, h, (tx, ty, tz), ry) — t the bottom centre, as a KITTI label — whose
+    boxes do not come within 2 * RAW_MARGIN + 2 * RAW_RELAX of one another.  A third of the points lies RAW_MARGIN inside the
+    objects, the rest on the ground and in clutter over a region wider than the crop on every side, RAW_MARGIN outside every
+    relaxed box."""
+    import numpy as np
+    n_obj = n_points // 3
+    which = rs.randint(len(objects), size=n_obj)
+    pts, labels = [], []
+    for k, (l, w, h, t, ry) in enumerate(objects):
+        m = int((which == k).sum())
+        half = np.array([l / 2 - RAW_MARGIN, 0.0, w / 2 - RAW_MARGIN])
+        local = (rs.rand(m, 3) - 0.5) * 2 * half
+        local[:, 1] = -RAW_MARGIN - rs.rand(m) * (h - 2 * RAW_MARGIN)
+        pts.append(local @ _rot_y_np(ry).T + np.asarray(t))
+        labels.append(np.full(m, k + 1, dtype=np.int32))
+    n_bg = n_points - n_obj
+    z = -5.0 + 50.0 * rs.rand(n_bg)
+    x = np.where(rs.rand(n_bg) < 0.8, z * (rs.rand(n_bg) - 0.5) * 1.9, (rs.rand(n_bg) - 0.5) * 60.0)
+    y = np.where(rs.rand(n_bg) < 0.6, 1.65 + (rs.rand(n_bg) - 0.5) * 0.06, 1.6 - 2.6 * rs.rand(n_bg))
+    bg = np.stack([x, y, z], 1)
+    free = np.ones(n_bg, dtype=bool)
+    grow = RAW_RELAX + RAW_MARGIN + 0.01
+    for l, w, h, t, ry in objects:
+        q = (bg - np.asarray(t)) @ _rot_y_np(-ry).T
+        free &= ~((np.abs(q[:, 0]) < l / 2 + grow) & (q[:, 1] > -h - grow) & (q[:, 1] < grow) & (np.abs(q[:, 2]) < w / 2 + grow))
+    pts.append(bg[free])
+    labels.append(np.zeros(int(free.sum()), dtype=np.int32))
+    pts, labels = np.concatenate(pts), np.concatenate(labels)
+    perm = rs.permutation(pts.shape[0])
+    return pts[perm], labels[perm]
+
+
+def _camera_objects(rs, n):
+    """n upright boxes (l, w, h, t, ry) on the ground in front of the camera, one per 7-m slot, so that none comes near another;
+    every number has the two decimals a label file keeps."""
+    import numpy as np
+    slots = [(x, z) for z in (10.0, 17.0, 24.0, 31.0) for x in (-7.0, 0.0, 7.0) if abs(x) < 0.55 * z]
+    order = rs.permutation(len(slots))[:n]
+
+    def r2(v):
+        return float("%.2f" % v)
+    return [(r2(3.2 + 1.2 * rs.rand()), r2(1.5 + 0.4 * rs.rand()), r2(1.4 + 0.4 * rs.rand()),
+             (r2(slots[i][0] + rs.rand() - 0.5), 1.65, r2(slots[i][1] + rs.rand() - 0.5)), r2((rs.rand() - 0.5) * 2 * np.pi))
+            for i in order]
+
+
+def _calib_lines(entries):
+    import numpy as np
+    return "".join("%s: %s\n" % (key, " ".join("%.12e" % v for v in np.asarray(value, dtype=np.float64).reshape(-1)))
+                   for key, value in entries)
+
+
+def write_kittidet_raw_root(root, n_frames, n_points, seed=9000):
+    """`n_frames` raw KITTI-Det frames under <root>/training: velodyne/%06d.bin (N, 4) f32, calib/%06d.txt (P0 .. P3, R0_rect,
+    Tr_velo_to_cam, Tr_imu_to_velo), label_2/%06d.txt (a Pedestrian, three Cars and a DontCare line, in an order that gives the
+    Cars the ids 2, 4, 5) and image_2/%06d.png, a blank 1242 x 375 — what process_kittidet reads.  Returns a list of frames
+    {"calib": the matrices as the file holds them, "labels": (N,) i32 the label-line id of the Car a point lies in, else 0
+    (the Pedestrian's points included), "objects": per label line (type, h, w, l, tx, ty, tz, ry) as the line holds them}."""
+    import os
+
+    import numpy as np
+    from PIL import Image
+    base = os.path.join(root, "training")
+    for sub in ("velodyne", "calib", "label_2", "image_2"):
+        os.makedirs(os.path.join(base, sub), exist_ok=True)
+    frames = []
+    for i in range(n_frames):
+        rs = np.random.RandomState(seed + i)
+        calib = make_kitti_calibration(seed + i)
+        boxes = _camera_objects(rs, 4)
+        types = ["Pedestrian", "Car", "DontCare", "Car", "Car"]
+        rect, which = _camera_scene(n_points, rs, boxes)
+        line_of_box = [0, 1, 3, 4]                                      # the label line of box k
+        labels = np.zeros(rect.shape[0], dtype=np.int32)
+        for k in (1, 2, 3):
+            labels[which == k + 1] = line_of_box[k] + 1
+        velo = _rect_to_velo(rect, calib)
+        scan = np.concatenate([velo, rs.rand(velo.shape[0], 1)], 1).astype(np.float32)
+        scan.tofile(os.path.join(base, "velodyne", "%06d.bin" % i))
+        with open(os.path.join(base, "calib", "%06d.txt" % i), "w") as f:
+            f.write(_calib_lines([("P0", calib["P"]), ("P1", calib["P"]), ("P2", calib["P"]), ("P3", calib["P"]),
+                                  ("R0_rect", calib["R0"]), ("Tr_velo_to_cam", calib["V2C"]), ("Tr_imu_to_velo", np.eye(3, 4))]))
+        lines, objects, b = [], [], 0
+        for kind in types:
+            if kind == "DontCare":
+                lines.append("DontCare -1 -1 -10 503.89 169.71 590.61 190.13 -1 -1 -1 -1000 -1000 -1000 -10")
+                objects.append(("DontCare", -1.0, -1.0, -1.0, -1000.0, -1000.0, -1000.0, -10.0))
+                continue
+            l, w, h, t, ry = boxes[b]
+            b += 1
+            text = "%s 0.00 0 -1.57 100.00 120.00 300.00 220.00 %.2f %.2f %.2f %.2f %.2f %.2f %.2f" % (kind, h, w, l, t[0], t[1], t[2], ry)
+            lines.append(text)
+            objects.append((kind,) + tuple(float(v) for v in text.split(" ")[8:15]))
+        with open(os.path.join(base, "label_2", "%06d.txt" % i), "w") as f:
+            f.write("\n".join(lines) + "\n")
+        Image.new("RGB", KITTI_IMAGE_SIZE).save(os.path.join(base, "image_2", "%06d.png" % i))
+        frames.append({"calib": calib, "labels": labels, "objects": objects})
+    return frames
+
+
+SEMANTICKITTI_OBJECTS = ((10, 1), (252, 2), (18, 1), (30, 1))   # (class, instance) of the four objects: car, moving-car, truck, person
+SEMANTICKITTI_GROUND = 40                                       # road, instance 0
+
+
+def write_semantickitti_raw_root(root, n_frames, n_points, sequences=(0,), seed=9100):
+    """Raw SemanticKITTI sequences under <root>/sequences/%02d: velodyne/%06d.bin (N, 4) f32, labels/%06d.label (N,) 32-bit words
+    — the class in the low half, the instance id in the high half: four objects of SEMANTICKITTI_OBJECTS, of which the person is
+    not among the classes the preparation keeps, and road — and one calib.txt (P0 .. P3, Tr; no R0) — what process_semantickitti
+    reads.  Returns {sequence: {"calib": the matrices as the file holds them, "labels": [per frame the (N,) i32 label words]}}."""
+    import os
+
+    import numpy as np
+    out = {}
+    for s, sequence in enumerate(sequences):
+        base = os.path.join(root, "sequences", "%02d" % sequence)
+        for sub in ("velodyne", "labels"):
+            os.makedirs(os.path.join(base, sub), exist_ok=True)
+        calib = make_kitti_calibration(seed + 1000 * s, with_r0=False)
+        with open(os.path.join(base, "calib.txt"), "w") as f:
+            f.write(_calib_lines([("P0", calib["P"]), ("P1", calib["P"]), ("P2", calib["P"]), ("P3", calib["P"]), ("Tr", calib["V2C"])]))
+        words = np.array([SEMANTICKITTI_GROUND] + [c | (i << 16) for c, i in SEMANTICKITTI_OBJECTS], dtype=np.int32)
+        labels = []
+        for i in range(n_frames):
+            rs = np.random.RandomState(seed + 1000 * s + i + 1)
+            rect, which = _camera_scene(n_points, rs, _camera_objects(rs, len(SEMANTICKITTI_OBJECTS)))
+            scan = np.concatenate([_rect_to_velo(rect, calib), rs.rand(rect.shape[0], 1)], 1).astype(np.float32)
+            scan.tofile(os.path.join(base, "velodyne", "%06d.bin" % i))
+            words[which].tofile(os.path.join(base, "labels", "%06d.label" % i))
+            labels.append(words[which])
+        out[sequence] = {"calib": calib, "labels": labels}
+    return out
+
+
+WAYMO_CLASSES = ("Vehicle", "Pedestrian", "Cyclist")
+# the boxes of a synthetic raw Waymo sequence, in this order: (name, counted points; 0 = annotated as empty).  Labelled are the
+# first five; `unknown`, the box annotated as empty and the Sign hold points too, which must come out unlabelled.
+WAYMO_RAW_BOXES = (("Vehicle", 1), ("Vehicle", 1), ("Pedestrian", 1), ("Cyclist", 1), ("Vehicle", 1), ("unknown", 1), ("Vehicle", 0),
+                   ("Sign", 1))
+
+
+def write_waymo_raw_root(root, n_sequences, n_frames, n_points, seed=9200, data_tag="waymo_processed_data", flow_tag="scene_flow",
+                         split="train", box_dtype="float64"):
+    """Raw Waymo sequences as the info-file pipeline leaves them: <root>/<data_tag>/<seq>/<seq>.pkl, a list of frame infos
+    {point_cloud: {lidar_sequence, sample_idx}, pose (4, 4) f64 sensor-to-world, annos: {name, gt_boxes_lidar (K, 7) [x, y, z, l, w,
+    h, heading], obj_ids, num_points_in_gt}}, <root>/<data_tag>/<seq>/%04d.npy (N, 6) f32 [x, y, z, intensity, elongation, NLZ
+    flag] in lidar coordinates (x forward, y left, z up) and <root>/<flow_tag>/<seq>/%04d.npy (N, 4) f32 velocities in m/s, plus
+    <root>/<split>.txt with the names as `<seq>.tfrecord` and one name that is not on disk — what process_waymo reads.
+    The world is static but for box 4, which drives along x; the sensor moves under known poses (yaw about z, shift in the
+    plane).  Every frame samples the world anew: a ground sheet at z = -1.8 wider than every range test, the boxes of
+    WAYMO_RAW_BOXES filled RAW_MARGIN inside the extents the reference tests (l on x, h on y, w on z), in a per-frame order of the
+    annotations, and about a tenth of the points flagged out through column 5.
+    Returns {seq: [per frame {"box": (N,) i32 index + 1 into WAYMO_RAW_BOXES of the box a point was drawn in (0: ground),
+    "static": (N,) bool, "pose": (4, 4)}]}."""
+    import os
+    import pickle
+
+    import numpy as np
+    names, out = [], {}
+    n_box = len(WAYMO_RAW_BOXES)
+    for s in range(n_sequences):
+        seq = "segment-%04d_with_camera_labels" % s
+        rs = np.random.RandomState(seed + s)
+        d_data, d_flow = os.path.join(root, data_tag, seq), os.path.join(root, flow_tag, seq)
+        os.makedirs(d_data, exist_ok=True)
+        os.makedirs(d_flow, exist_ok=True)
+        # world boxes, one per 7-m slot in front of the start: centre, (l, w, h), heading; the reference's extents are (l, h, w)
+        slots = [(x, y) for x in (9.0, 16.0, 23.0) for y in (-7.0, 0.0, 7.0)]
+        order = rs.permutation(len(slots))[:n_box]
+        dims = np.stack([2.0 + 2.5 * rs.rand(n_box), 1.2 + 0.8 * rs.rand(n_box), 1.2 + 0.8 * rs.rand(n_box)], 1)
+        centres = np.stack([np.array([slots[i][0] for i in order]) + rs.rand(n_box) - 0.5,
+                            np.array([slots[i][1] for i in order]) + rs.rand(n_box) - 0.5, -1.8 + 0.2 + dims[:, 1] / 2 + 0.3 * rs.rand(n_box)], 1)
+        headings = (rs.rand(n_box) - 0.5) * 2 * np.pi
+        velocity = np.zeros((n_box, 3))
+        velocity[4] = [3.0, 0.0, 0.0]                      # m/s in the world; a frame is 0.1 s
+        tracks = ["%s_trk%02d" % (seq[:12], k) for k in range(n_box)]
+        infos, frames, yaw, position = [], [], 0.0, np.zeros(3)
+        for t in range(n_frames):
+            pose = np.eye(4)
+            pose[:3, :3], pose[:3, 3] = _rot_z_np(yaw), position
+            n = n_points + int(rs.randint(-(n_points // 20), n_points // 20 + 1))
+            n_obj = n // 3
+            which = rs.randint(n_box, size=n_obj)
+            now = centres + 0.1 * t * velocity
+            half = dims[:, [0, 2, 1]] / 2 - RAW_MARGIN                  # x: l, y: h, z: w
+            local = (rs.rand(n_obj, 3) - 0.5) * 2 * half[which]
+            c, sn = np.cos(headings[which]), np.sin(headings[which])
+            world = np.stack([c * local[:, 0] - sn * local[:, 1], sn * local[:, 0] + c * local[:, 1], local[:, 2]], 1) + now[which]
+            ground = np.stack([position[0] - 20.0 + 95.0 * rs.rand(n - n_obj), position[1] + (rs.rand(n - n_obj) - 0.5) * 130.0,
+                               -1.8 + (rs.rand(n - n_obj) - 0.5) * 0.06], 1)
+            world = np.concatenate([world, ground])
+            box = np.concatenate([which + 1, np.zeros(n - n_obj, dtype=np.int64)]).astype(np.int32)
+            vel = np.concatenate([velocity[which], np.zeros((n - n_obj, 3))])
+            perm = rs.permutation(n)
+            world, box, vel = world[perm], box[perm], vel[perm]
+            pc = (world - position) @ pose[:3, :3]                      # R^T (w - t), row-wise
+            flag = np.where(rs.rand(n) < 0.1, rs.randint(0, 2, size=n), -1).astype(np.float64)
+            np.save(os.path.join(d_data, "%04d.npy" % t), np.concatenate([pc, rs.rand(n, 2), flag[:, None]], 1).astype(np.float32))
+            np.save(os.path.join(d_flow, "%04d.npy" % t), np.concatenate([vel @ pose[:3, :3], box[:, None] > 0], 1).astype(np.float32))
+            listed = rs.permutation(n_box)
+            gt = np.concatenate([(now - position) @ pose[:3, :3], dims, (headings - yaw)[:, None]], 1)[listed]
+            infos.append({"point_cloud": {"lidar_sequence": seq, "sample_idx": t}, "pose": pose.copy(),
+                          "annos": {"name": np.array([WAYMO_RAW_BOXES[k][0] for k in listed]),
+                                    "gt_boxes_lidar": gt.astype(box_dtype),
+                                    "obj_ids": np.array([tracks[k] for k in listed]),
+                                    "num_points_in_gt": np.array([WAYMO_RAW_BOXES[k][1] * int((box == k + 1).sum()) for k in listed])}})
+            frames.append({"box": box, "static": box != 5, "pose": pose.copy()})
+            yaw += (rs.rand() - 0.5) * 0.04
+            position = position + np.array([0.6 + 0.4 * rs.rand(), (rs.rand() - 0.5) * 0.2, 0.0])
+        with open(os.path.join(d_data, seq + ".pkl"), "wb") as f:
+            pickle.dump(infos, f)
+        names.append(seq)
+        out[seq] = frames
+    with open(os.path.join(root, split + ".txt"), "w") as f:
+        f.write("\n".join(["%s.tfrecord" % n for n in names] + ["segment-absent_with_camera_labels.tfrecord"]) + "\n")
+    return out
