@@ -638,6 +638,30 @@ int ogc_conv1x1_dgrad_adjoint(int b, int cin, int cout, int hw, int relu, const 
                               const float *y_prev, const float *pa, const float *pb, const float *coef, float *grad_prev,
                               ogc_stream_t stream);
 
+/* The first two layers of a set-abstraction MLP,  y2 = conv(relu(GroupNorm(y1)), w),  y1 = conv(x0, w1),  without y1 or its
+ * gradient in memory (ogc_amd/csrc/first_conv.h).  x0 (b, c0, hw) is the grouped input, c0 <= 8; w1 (c1, c0).  Every kernel
+ * rebuilds the values of y1 it would have loaded: w1[r][0] * x0[0], then fused multiply-adds over the channels ascending — what
+ * ogc_conv1x1_gemm_gnstats stores, bit for bit.  All four: c1 <= 64, hw % 64 == 0, x0 16-byte aligned, c1 * hw < 2^31.
+ *   ogc_first_conv_stats: the statistics of y1 for its GroupNorm, in ogc_conv1x1_gemm_gnstats's layout (overwritten);
+ *       (c1 / groups) % 4 == 0, groups <= 32.
+ *   ogc_conv1x1_gemm_affine_first: ogc_conv1x1_gemm_affine with in = y1 (M output channels, K = c1, groups >= 1: the
+ *       statistics of the output as there).  Given the same pa, pb the output equals ogc_conv1x1_gemm_affine's on a stored y1.
+ *   ogc_conv1x1_wgrad_moments_first: ogc_conv1x1_wgrad_moments with y_prev = y1 (cin = c1).
+ *   ogc_conv1x1_dgrad_adjoint_first: ogc_conv1x1_dgrad_adjoint with y_prev = y1 (cin = c1, cout <= 64) whose result
+ *       g1 = alpha mask (w^T grad_y) + c2 y1 + c3 is not stored: grad_w1 (c1, c0) = sum over samples and positions of g1 x0^T,
+ *       the weight gradient of the first convolution (overwritten; fp32 atomic sums). */
+int ogc_first_conv_stats(int b, int c1, int c0, int hw, int groups, const float *x0, const float *w1, double *stats,
+                         ogc_stream_t stream);
+int ogc_conv1x1_gemm_affine_first(int b, int M, int K, int hw, int relu, int groups, int c0, const float *w, const float *x0,
+                                  const float *w1, const float *pa, const float *pb, float *out, double *stats,
+                                  ogc_stream_t stream);
+int ogc_conv1x1_wgrad_moments_first(int b, int cin, int cout, int hw, int relu, int c0, const float *x0, const float *w1,
+                                    const float *pa, const float *pb, const float *grad_y, float *moments,
+                                    ogc_stream_t stream);
+int ogc_conv1x1_dgrad_adjoint_first(int b, int cin, int cout, int hw, int relu, int c0, const float *w, const float *grad_y,
+                                    const float *x0, const float *w1, const float *pa, const float *pb, const float *coef,
+                                    float *grad_w1, ogc_stream_t stream);
+
 /* The tail of a set-abstraction MLP backwards, without the dense gradient in between:  last layer
  *   y = conv(relu(GroupNorm(y_prev)))  followed by  out = max over the neighbourhood of relu(GroupNorm'(y))
  * (utils/pointnet2_util.py:38-42).  The gradient of that pooled GroupNorm w.r.t. y is affine in y except at the arg-max

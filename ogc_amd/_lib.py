@@ -111,6 +111,10 @@ SIGNATURES = {
     "ogc_conv1x1_wgrad_moments": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_gn_moments_combine": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_conv1x1_dgrad_adjoint": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_first_conv_stats": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
+    "ogc_conv1x1_gemm_affine_first": [_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_conv1x1_wgrad_moments_first": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_conv1x1_dgrad_adjoint_first": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_norm_maxpool_bwd_sparse": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _vp],
     "ogc_group_norm_maxpool_bwd_ext": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -3,6 +3,7 @@
 #include "conv1x1_shared.h"
 #include "act_io.h"
 #include "conv1x1_epilogue.h"
+#include "first_conv.h"
 
 int ogc_g_matmul_bf16 = 0;
 
@@ -39,7 +40,10 @@ namespace {
 // accumulator columns of a lane and the pool_s / 4 lanes of a DPP row first, then the smallest index attaining them.
 // IT / OT: element types of `in` and `out` (float, or ogc_bf16 for activations kept in 16 bits: act_io.h); the statistics and
 // the extremes are then those of the ROUNDED outputs.
-template <bool TRANSPOSE_A, int KQ, bool STATS, bool PRO, bool BF, bool POOL = false, typename IT = float, typename OT = float>
+// FIRST (0: off, else the CP of first_conv.h): `in` is the output of a first convolution that was never stored — the tile is
+// rebuilt from first.x0 and first.w1 (K = c1 <= 64 rows of W1 in LDS), everything after the load is the same.
+template <bool TRANSPOSE_A, int KQ, bool STATS, bool PRO, bool BF, bool POOL = false, typename IT = float, typename OT = float,
+          int FIRST = 0>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M, int K, int hw, int groups,
                                                                           const float *__restrict__ w, // (Cout, Cin)
                                                                           const IT *__restrict__ in,
@@ -47,8 +51,9 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M,
                                                                           double *__restrict__ stats,
                                                                           const float *__restrict__ pa,
                                                                           const float *__restrict__ pb, int pro_relu,
-                                                                          PoolOut pool = PoolOut()) {
+                                                                          PoolOut pool = PoolOut(), FirstIn first = FirstIn()) {
     extern __shared__ __attribute__((aligned(16))) float a_lds[]; // [64][ogc_a_ld(Kq)]: the current 64-row tile of A (conv_stage.h)
+    __shared__ __attribute__((aligned(16))) float s_w1[FIRST ? FC_MAX_ROWS * FC_MAX_C0 : 4];
     __shared__ double s_stats[STATS ? 64 : 1];                    // [groups][2]
     __shared__ __attribute__((aligned(16))) float s_sign[POOL ? 64 : 4]; // POOL: -1 for the tile's rows whose next scale is negative
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -62,10 +67,25 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M,
     if (STATS && threadIdx.x < 2 * groups) s_stats[threadIdx.x] = 0.0;
 
     float4 xin[KQ];
+    if constexpr (FIRST > 0) {
+        static_assert(KQ * 4 <= FC_MAX_ROWS && sizeof(IT) == 4 && !TRANSPOSE_A, "first-layer form: fp32, at most 64 rows of W1");
+        ogc_first_stage_w1<WG_WAVES * OGC_WAVE>(s_w1, first.w1, K, first.c0);
+        float4 x0v[FIRST];
+        ogc_first_load_raw<FIRST>(x0v, first.x0 + (size_t)b * first.c0 * hw + (live ? p0 + 4 * j : 0), first.c0, hw);
+        ogc_first_mask<FIRST>(x0v, first.c0, live);
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < KQ; ++q) { // rows beyond K meet zero weights in s_w1: exact zeros, as the loads of the stored form
+            float w1r[FIRST];
+            ogc_first_w1_row<FIRST>(w1r, s_w1, q * 4 + kk);
+            xin[q] = ogc_first_row<FIRST>(x0v, w1r);
+        }
+    } else {
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
         const int row = q * 4 + kk;
         xin[q] = (live && q < Kq && row < K) ? ogc_ld4(inb + (size_t)row * hw + p0 + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     }
     if (PRO) { // a second pass, so that all loads above are in flight before the first one is waited for; in chunks
                // of eight rows so that the coefficients stay transient in wide layers (no spare registers there)
@@ -783,4 +803,162 @@ extern "C" int ogc_conv1x1_gemm_affine_pool_h(int b, int M, int K, int hw, int r
                                               ogc_stream_t stream) {
     return gemm_affine_pool_impl<ogc_bf16>("ogc_conv1x1_gemm_affine_pool_h", b, M, K, hw, relu, groups, nsample, w, in, pa, pb,
                                            next_gamma, out, stats, yext, aext, stream);
+}
+
+// ---- the first two layers of a level's MLP without the first convolution's output (first_conv.h) ------------------------------
+namespace {
+
+// GroupNorm statistics of y1 = conv(x0, w1) from x0 alone, with the fp32 partial sums of the matrix kernel's epilogue: a wave owns 64
+// positions, lane (j, kk) rebuilds rows 16 a + 4 kk .. + 3 at positions 4 j .. 4 j + 3 — the values conv1x1_gemm_kernel holds there —
+// and sums them in its order (rows, then positions; then the 16 lanes of the DPP row).  Those 256-value sums are the same
+// numbers; from there on everything is fp64 (per lane over the workgroup's run of tiles, LDS, one atomic per (group, statistic) and
+// workgroup into copy blockIdx.x % GN_SLOTS), so the result differs from ogc_conv1x1_gemm_gnstats's only as two runs of that
+// kernel differ from each other: in the order of fp64 additions.  (A GroupNorm coefficient one ulp away moves activations across
+// ReLU and max-pool gates: tests/test_truth_f64_gpu.py notices.)
+template <int CP>
+__global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void first_conv_stats_kernel(int c1, int c0, int hw, int groups, int run,
+                                                                              const float *__restrict__ x0,
+                                                                              const float *__restrict__ w1,
+                                                                              double *__restrict__ stats) {
+    __shared__ __attribute__((aligned(16))) float s_w1[FC_MAX_ROWS * FC_MAX_C0];
+    __shared__ double s_stats[64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 15, kk = lane >> 4;
+    const int b = blockIdx.y;
+    ogc_first_stage_w1<WG_WAVES * OGC_WAVE>(s_w1, w1, c1, c0);
+    if (threadIdx.x < 64) s_stats[threadIdx.x] = 0.0;
+    __syncthreads();
+    const float *xb = x0 + (size_t)b * c0 * hw;
+    const int nblk = (c1 + 15) >> 4;
+    double dsm[4] = {0.0, 0.0, 0.0, 0.0}, dsq[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int it = 0; it < run; ++it) {
+        const int p0 = ((blockIdx.x * run + it) * WG_WAVES + wave) * 64;
+        const bool live = p0 < hw; // (a wave that is not live adds zeros)
+        float4 x[CP];
+        ogc_first_load_raw<CP>(x, xb + (live ? p0 + 4 * j : 0), c0, hw);
+        ogc_first_mask<CP>(x, c0, live);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            if (a < nblk) {
+                float sm = 0.f, sq = 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { // rows beyond c1 meet zero weights: exact zeros, as in the matrix kernel
+                    float w[CP];
+                    ogc_first_w1_row<CP>(w, s_w1, a * 16 + kk * 4 + r);
+                    const float4 v = ogc_first_row<CP>(x, w);
+                    sm += v.x; sq += v.x * v.x;
+                    sm += v.y; sq += v.y * v.y;
+                    sm += v.z; sq += v.z * v.z;
+                    sm += v.w; sq += v.w * v.w;
+                }
+                sm += ogc_dpp_f32<0xB1>(sm); sq += ogc_dpp_f32<0xB1>(sq);
+                sm += ogc_dpp_f32<0x4E>(sm); sq += ogc_dpp_f32<0x4E>(sq);
+                sm += ogc_dpp_f32<0x141>(sm); sq += ogc_dpp_f32<0x141>(sq);
+                sm += ogc_dpp_f32<0x140>(sm); sq += ogc_dpp_f32<0x140>(sq);
+                dsm[a] += (double)sm;
+                dsq[a] += (double)sq;
+            }
+        }
+    }
+    const int cpg = c1 / groups;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int m = a * 16 + kk * 4;
+        if (j == 0 && m < c1) {
+            atomicAdd(&s_stats[2 * (m / cpg)], dsm[a]);
+            atomicAdd(&s_stats[2 * (m / cpg) + 1], dsq[a]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * groups) {
+        double *dst = stats + ((size_t)(blockIdx.x % GN_SLOTS) * gridDim.y + b) * 2 * groups;
+        atomicAdd(dst + threadIdx.x, s_stats[threadIdx.x]);
+    }
+}
+
+// the preconditions the four first-layer entry points share
+int first_check(const char *name, int b, int c1, int c0, int hw, const float *x0, const float *w1) {
+    OGC_REQUIRE(b >= 0 && c1 >= 1 && c0 >= 1 && hw >= 1, "%s: bad shape", name);
+    OGC_REQUIRE(x0 && w1, "%s: null pointer", name);
+    if (c0 > FC_MAX_C0 || c1 > FC_MAX_ROWS || (hw & 63) != 0 || ((uintptr_t)x0 & 15) != 0) {
+        ogc_set_error("%s: needs c0 <= %d, c1 <= %d, hw %% 64 == 0 and a 16-byte aligned x0 (c0=%d, c1=%d, hw=%d)", name, FC_MAX_C0,
+                      FC_MAX_ROWS, c0, c1, hw);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    OGC_REQUIRE((long long)FC_MAX_ROWS * hw < (1ll << 31) && b <= 32768, "%s: one sample exceeds 32-bit indexing", name);
+    return OGC_OK;
+}
+
+} // namespace
+
+int ogc_first_check(const char *name, int b, int c1, int c0, int hw, const float *x0, const float *w1) {
+    return first_check(name, b, c1, c0, hw, x0, w1);
+}
+
+extern "C" int ogc_first_conv_stats(int b, int c1, int c0, int hw, int groups, const float *x0, const float *w1, double *stats,
+                                    ogc_stream_t stream) {
+    const int rc = first_check("ogc_first_conv_stats", b, c1, c0, hw, x0, w1);
+    if (rc != OGC_OK) return rc;
+    OGC_REQUIRE(stats, "ogc_first_conv_stats: null pointer");
+    if (groups < 1 || groups > 32 || c1 % groups != 0 || (c1 / groups) % 4 != 0) {
+        ogc_set_error("ogc_first_conv_stats: needs 1 <= groups <= 32 and (c1 / groups) %% 4 == 0 (c1=%d, groups=%d)", c1, groups);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    if (b == 0) return OGC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (ogc_zero_async(stats, sizeof(double) * 2 * GN_SLOTS * (size_t)b * groups, s) != hipSuccess) {
+        ogc_set_error("ogc_first_conv_stats: memset failed");
+        return OGC_ERR_LAUNCH;
+    }
+    // ~2048 workgroups over the chip, each walking a run of at most eight consecutive 256-position tiles of one sample
+    const int tiles = ogc_divup(hw, 64 * WG_WAVES);
+    int run = ogc_divup((long long)tiles * b, 2048);
+    if (run > 8) run = 8;
+    dim3 grid(ogc_divup(tiles, run), b), block(WG_WAVES * OGC_WAVE);
+    const int cp = ogc_first_cp(c0);
+    if (cp == 3) hipLaunchKernelGGL(first_conv_stats_kernel<3>, grid, block, 0, s, c1, c0, hw, groups, run, x0, w1, stats);
+    else if (cp == 6) hipLaunchKernelGGL(first_conv_stats_kernel<6>, grid, block, 0, s, c1, c0, hw, groups, run, x0, w1, stats);
+    else hipLaunchKernelGGL(first_conv_stats_kernel<8>, grid, block, 0, s, c1, c0, hw, groups, run, x0, w1, stats);
+    OGC_CHECK_LAUNCH("ogc_first_conv_stats");
+    return OGC_OK;
+}
+
+// ogc_conv1x1_gemm_affine with output statistics on in = conv(x0, w1), which is rebuilt while the tile is loaded: the tile kernel
+// (the persistent form of conv1x1_h.hip gives the same bits where it would have run: its test pins that).
+extern "C" int ogc_conv1x1_gemm_affine_first(int b, int M, int K, int hw, int relu, int groups, int c0, const float *w,
+                                             const float *x0, const float *w1, const float *pa, const float *pb, float *out,
+                                             double *stats, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_gemm_affine_first";
+    int rc = first_check(name, b, K, c0, hw, x0, w1);
+    if (rc != OGC_OK) return rc;
+    OGC_REQUIRE(M >= 1 && w && pa && pb && out && stats, "%s: bad shape or null pointer", name);
+    if (groups < 1 || groups > 32 || M % groups != 0 || (M / groups) % 4 != 0 || ((uintptr_t)out & 15) != 0 || g_matmul_bf16) {
+        ogc_set_error("%s: needs fp32 operands, 1 <= groups <= 32, (M / groups) %% 4 == 0 and a 16-byte aligned output (M=%d, "
+                      "groups=%d)", name, M, groups);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    OGC_REQUIRE((long long)M * hw < (1ll << 31) && b <= 65535, "%s: one sample exceeds 32-bit indexing", name);
+    if (b == 0) return OGC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (ogc_zero_async(stats, sizeof(double) * 2 * GN_SLOTS * (size_t)b * groups, s) != hipSuccess) {
+        ogc_set_error("%s: memset failed", name);
+        return OGC_ERR_LAUNCH;
+    }
+    const int Kq = (K + 3) / 4, cp = ogc_first_cp(c0);
+    const size_t lds = (size_t)64 * ogc_a_ld(Kq) * sizeof(float);
+    dim3 grid(ogc_divup(hw, 64 * WG_WAVES), b);
+    FirstIn first;
+    first.x0 = x0; first.w1 = w1; first.c0 = c0;
+#define OGC_GEMM_FIRST(KQV, CPV)                                                                                           \
+    hipLaunchKernelGGL((conv1x1_gemm_kernel<false, KQV, true, true, false, false, float, float, CPV>), grid,               \
+                       dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, groups, w, (const float *)nullptr, out, stats, pa, pb, relu, \
+                       PoolOut(), first)
+    if (Kq <= 8) {
+        if (cp == 3) OGC_GEMM_FIRST(8, 3); else if (cp == 6) OGC_GEMM_FIRST(8, 6); else OGC_GEMM_FIRST(8, 8);
+    } else {
+        if (cp == 3) OGC_GEMM_FIRST(16, 3); else if (cp == 6) OGC_GEMM_FIRST(16, 6); else OGC_GEMM_FIRST(16, 8);
+    }
+#undef OGC_GEMM_FIRST
+    OGC_CHECK_LAUNCH(name);
+    return OGC_OK;
 }

@@ -23,6 +23,7 @@
 //   ogc_conv1x1_dgrad_adjoint   g_prev
 #include "conv1x1_shared.h" // v4f, WG_WAVES, ogc_pooled_grad, the operand precision switch ogc_g_matmul_bf16 (conv1x1.hip)
 #include "act_io.h"
+#include "first_conv.h"
 
 namespace {
 
@@ -34,7 +35,9 @@ namespace {
 // convolution's OUTPUT y, and g_y[row, pos] = fmaf(c2, y, c3) + (pos % S == arg ? ag : 0) is rebuilt from coef2[b, row] =
 // (c2, c3) and inj[b, row, pos / S] = (ag, arg) — a step's 16 positions lie inside one neighbourhood (S = 16, 32, 64).
 // AT: element type of x and dy (float / ogc_bf16: act_io.h).
-template <int COB, int CIB, bool POOLED, typename AT = float>
+// FIRST (0: off, else the CP of first_conv.h): x is the output of a first convolution that was never stored; a lane rebuilds its
+// CIB float4 of it from the x0 values at its four positions (loaded in x's place) and the rows of W1 it holds in registers.
+template <int COB, int CIB, bool POOLED, typename AT = float, int FIRST = 0>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int cin, int cout, int hw, int chunks,
                                                                            int steps_per_wave, int relu,
                                                                            const AT *__restrict__ x,   // y_prev (B, cin, hw)
@@ -44,15 +47,17 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
                                                                            const float2 *__restrict__ coef2, // (B, cout)
                                                                            const float2 *__restrict__ inj,   // (B, cout, hw >> s_shift)
                                                                            int s_shift,
-                                                                           float *__restrict__ hm) {      // (B, 2, cout, cin)
+                                                                           float *__restrict__ hm,        // (B, 2, cout, cin)
+                                                                           FirstIn first = FirstIn()) {
+    constexpr int XN = FIRST ? FIRST : CIB; // float4 a lane loads per step in x's place
     __shared__ float red[WG_WAVES][COB * CIB * 256]; // one slab per wave (see conv1x1_wgrad_kernel), H then H2
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 15, k = lane >> 4;
     const int img = blockIdx.x / chunks, chunk = blockIdx.x - img * chunks;
     const int co0 = blockIdx.y * (16 * COB), ci0 = blockIdx.z * (16 * CIB);
     const int steps_per_img = hw >> 4;
-    const int first = (chunk * WG_WAVES + wave) * steps_per_wave;
-    const int mine = max(0, min(steps_per_wave, steps_per_img - first)); // this wavefront's steps: [first, first + mine)
+    const int first_step = (chunk * WG_WAVES + wave) * steps_per_wave;
+    const int mine = max(0, min(steps_per_wave, steps_per_img - first_step)); // this wavefront's steps: [first_step, first_step + mine)
 
     v4f acc1[COB][CIB], acc2[COB][CIB];
 #pragma unroll
@@ -62,8 +67,9 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
             acc1[a][c] = (v4f){0.f, 0.f, 0.f, 0.f};
             acc2[a][c] = (v4f){0.f, 0.f, 0.f, 0.f};
         }
-    int yrow[COB], xrow[CIB], jrow[COB];
+    int yrow[COB], xrow[XN], jrow[COB];
     float ca[CIB], cb[CIB], pc2[COB], pc3[COB];
+    float w1r[FIRST ? CIB : 1][FIRST ? FIRST : 1]; // FIRST: the rows of W1 of this lane's CIB channels (zeros beyond c0)
     const int centres = hw >> s_shift, smask = (1 << s_shift) - 1;
 #pragma unroll
     for (int a = 0; a < COB; ++a) {
@@ -80,24 +86,33 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
 #pragma unroll
     for (int c = 0; c < CIB; ++c) {
         const int ch = min(ci0 + c * 16 + i, cin - 1);
-        xrow[c] = ch * hw;
+        if constexpr (FIRST == 0) xrow[c] = ch * hw;
         ca[c] = aff_a[(size_t)img * cin + ch];
         cb[c] = aff_b[(size_t)img * cin + ch];
+        if constexpr (FIRST > 0) {
+#pragma unroll
+            for (int e = 0; e < FIRST; ++e) w1r[c][e] = e < first.c0 ? first.w1[ch * first.c0 + min(e, first.c0 - 1)] : 0.f;
+        }
+    }
+    if constexpr (FIRST > 0) { // one load shape per channel of x0; channels beyond c0 re-read the last one and are zeroed in fma16
+#pragma unroll
+        for (int e = 0; e < FIRST; ++e) xrow[e] = min(e, first.c0 - 1) * hw;
     }
     const AT *yb_ = dy + (size_t)img * cout * hw + 4 * k;
-    const AT *xb_ = x + (size_t)img * cin * hw + 4 * k;
-    int cur = min(first, steps_per_img - 1);
-    const int stop = min(first + mine, steps_per_img) - 1; // the walk stays on the wave's last step once it is reached
+    const AT *xb_ = FIRST ? reinterpret_cast<const AT *>(first.x0) + (size_t)img * first.c0 * hw + 4 * k
+                          : x + (size_t)img * cin * hw + 4 * k;
+    int cur = min(first_step, steps_per_img - 1);
+    const int stop = min(first_step + mine, steps_per_img) - 1; // the walk stays on the wave's last step once it is reached
     // Unconditional loads of one shape (see conv1x1_wgrad_kernel: a load under a per-lane condition makes the compiler wait
     // for ALL outstanding loads wherever it needs one, which serialises the ping-pong): rows beyond the tensors are clamped
     // onto the last row — they only reach rows / columns of H, H2 that are never stored — and steps beyond the wave's
     // share re-read its last step and are not computed with.
-    auto load = [&](float4(&yv)[COB], float4(&xv)[CIB], float2(&jv)[COB], int &jpos) { // step `cur`, then advance
+    auto load = [&](float4(&yv)[COB], float4(&xv)[XN], float2(&jv)[COB], int &jpos) { // step `cur`, then advance
         const int pb = cur * 16;
 #pragma unroll
         for (int a = 0; a < COB; ++a) yv[a] = ogc_ld4(yb_ + yrow[a] + pb);
 #pragma unroll
-        for (int c = 0; c < CIB; ++c) xv[c] = ogc_ld4(xb_ + xrow[c] + pb);
+        for (int c = 0; c < XN; ++c) xv[c] = ogc_ld4(xb_ + xrow[c] + pb);
         if (POOLED) {
 #pragma unroll
             for (int a = 0; a < COB; ++a) jv[a] = jb_[jrow[a] + (pb >> s_shift)];
@@ -105,15 +120,23 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
         }
         cur = min(cur + 1, max(stop, 0));
     };
-    auto fma16 = [&](float4(&yv)[COB], const float4(&xraw)[CIB], const float2(&jv)[COB], int jpos) {
+    auto fma16 = [&](float4(&yv)[COB], const float4(&xraw)[XN], const float2(&jv)[COB], int jpos) {
         if (POOLED) {
 #pragma unroll
             for (int a = 0; a < COB; ++a) ogc_pooled_grad(yv[a], pc2[a], pc3[a], jv[a], jpos); // (gn_maxpool_bwd_dx_kernel's expression)
         }
+        float4 x0v[FIRST ? FIRST : 1];
+        if constexpr (FIRST > 0) {
+#pragma unroll
+            for (int e = 0; e < FIRST; ++e) x0v[e] = xraw[e];
+            ogc_first_mask<FIRST>(x0v, first.c0, true);
+        }
         float4 m1[CIB], m2[CIB];
 #pragma unroll
         for (int c = 0; c < CIB; ++c) {
-            const float4 v = xraw[c];
+            float4 v;
+            if constexpr (FIRST > 0) v = ogc_first_row<FIRST>(x0v, w1r[c]);
+            else v = xraw[c];
             // mask = [a y + bb > 0] (relu); without relu: all ones
             const bool bx = relu ? fmaf(ca[c], v.x, cb[c]) > 0.f : true;
             const bool by = relu ? fmaf(ca[c], v.y, cb[c]) > 0.f : true;
@@ -137,7 +160,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
             }
     };
 
-    float4 ya[COB], xa[CIB], yb[COB], xb[CIB];
+    float4 ya[COB], xa[XN], yb[COB], xb[XN];
     float2 ja[COB], jb[COB];
     int pa_ = 0, pb_ = 0;
     load(ya, xa, ja, pa_);
@@ -327,9 +350,10 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments16_kernel(int
 }
 
 
-template <int COB, int CIB, typename AT>
+template <int COB, int CIB, typename AT, int FIRST = 0>
 void moments_launch(int b, int cin, int cout, int hw, int relu, const AT *x, const AT *dy, const float *pa,
-                    const float *pb, const float *coef2, const float *inj, int s_shift, float *hm, hipStream_t s) {
+                    const float *pb, const float *coef2, const float *inj, int s_shift, float *hm, hipStream_t s,
+                    FirstIn first = FirstIn()) {
     const int steps_per_img = sizeof(AT) == 2 ? hw >> 5 : hw >> 4; // (16-bit tensors: 32 positions per step)
     const int tiles = ogc_divup(cout, 16 * COB) * ogc_divup(cin, 16 * CIB);
     long long waves = (2048 / tiles) / b;            // wavefronts per sample and tile pair: ~2048 over the chip
@@ -347,6 +371,9 @@ void moments_launch(int b, int cin, int cout, int hw, int relu, const AT *x, con
         else
             hipLaunchKernelGGL((wgrad_moments16_kernel<COB, CIB, false>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
                                chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm);
+    } else if constexpr (FIRST > 0) {
+        hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT, FIRST>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
+                           chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm, first);
     } else {
         if (inj)
             hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, true, AT>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw, chunks,
@@ -439,7 +466,12 @@ __global__ __launch_bounds__(256) void moments_combine_kernel(int b, int cin, in
 // AT: element type of gy, yprev and out (float / ogc_bf16: act_io.h).
 // BF: operands rounded to bf16 on v_mfma_f32_16x16x16_bf16, staged as in conv1x1_gemm_kernel (the 16-bit instantiation: at 64 x 64
 // channels the fp32 MFMAs of a tile take 3.4 us per wavefront, twice what its halved bytes cost).
-template <int KQ, bool POOLED, typename AT = float, bool BF = false>
+// FIRST (0: off, else the CP of first_conv.h): y_prev is the output y1 = conv(x0, W1) of a first convolution that was never
+// stored (M = c1 <= 64): its rows are rebuilt from the lane's x0 values, and g_prev is not stored either — nothing reads it but
+// the weight gradient of that convolution, dW1[m][c] = sum_p g_prev[m][p] x0[c][p], which the epilogue forms from the four
+// positions it holds: summed over the 16 lanes of a DPP row, then over the workgroup's run of first.run position tiles in LDS,
+// then one fp32 atomic per element and workgroup into first.dw1.
+template <int KQ, bool POOLED, typename AT = float, bool BF = false, int FIRST = 0>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M, int K, int hw, int relu,
                                                                            const float *__restrict__ w,     // (K, M)
                                                                            const AT *__restrict__ gy,    // (B, K, hw)
@@ -450,19 +482,34 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                                                                            const float2 *__restrict__ coef2, // (B, K)
                                                                            const float2 *__restrict__ inj,   // (B, K, hw >> s_shift)
                                                                            int s_shift,
-                                                                           AT *__restrict__ out) {       // (B, M, hw)
+                                                                           AT *__restrict__ out,         // (B, M, hw)
+                                                                           FirstIn first = FirstIn()) {
     extern __shared__ __attribute__((aligned(16))) float a_lds[]; // [64][ogc_a_ld(Kq)] weights (conv_stage.h), then [64][5] coefficients
+    __shared__ __attribute__((aligned(16))) float s_w1[FIRST ? FC_MAX_ROWS * FC_MAX_C0 : 4]; // FIRST: W1, zero-padded
+    __shared__ float s_dw[FIRST ? FC_MAX_ROWS * FC_MAX_C0 : 4];                              // FIRST: the workgroup's share of dW1
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, kk = lane >> 4;
     const int b = blockIdx.y;
-    const int p0 = (blockIdx.x * WG_WAVES + wave) * 64;
     const int Kq = (K + 3) >> 2;
-    const bool live = p0 < hw;
     const AT *inb = gy + (size_t)b * K * hw;
     AT *outb = out + (size_t)b * M * hw;
     const AT *yb = yprev + (size_t)b * M * hw;
     const int a_ld = ogc_a_ld(Kq);
     float *cf = a_lds + (size_t)64 * a_ld;
+    if constexpr (FIRST > 0) { // (visible to all after the barriers in front of the first tile's MFMAs)
+        static_assert(!POOLED && !BF && sizeof(AT) == 4, "first-layer form: dense, fp32");
+        ogc_first_stage_w1<WG_WAVES * OGC_WAVE>(s_w1, first.w1, M, first.c0);
+        for (int t = threadIdx.x; t < FC_MAX_ROWS * FC_MAX_C0; t += WG_WAVES * OGC_WAVE) s_dw[t] = 0.f;
+    }
+    const int run = FIRST ? first.run : 1; // position tiles of 256 a workgroup walks (one, unless FIRST)
+    for (int it = 0; it < run; ++it) {
+    const int p0 = ((blockIdx.x * run + it) * WG_WAVES + wave) * 64;
+    const bool live = p0 < hw;
+    float4 x0v[FIRST ? FIRST : 1];
+    if constexpr (FIRST > 0) {
+        ogc_first_load_raw<FIRST>(x0v, first.x0 + (size_t)b * first.c0 * hw + (live ? p0 + 4 * j : 0), first.c0, hw);
+        ogc_first_mask<FIRST>(x0v, first.c0, live);
+    }
 
     float4 xin[KQ];
 #pragma unroll
@@ -513,6 +560,9 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
         }
     }
     for (int m0 = 0; m0 < M; m0 += 64) {
+        // FIRST: M <= 64 — the one row tile and the sample's coefficients are staged for the first position tile of the run and
+        // stay; the later tiles of the run meet no barrier and no dependent round trip besides their own loads
+        if (FIRST == 0 || it == 0) {
         __syncthreads(); // previous tile fully consumed
         if constexpr (BF) {
             ogc_stage_weight_tile_bf16<true, WG_WAVES, GQ>(a_lds, w, m0, M, K, Kq); // packed operands of w^T (conv_stage.h)
@@ -529,6 +579,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
             cf[t * 5 + 4] = in ? coef[((size_t)b * M + m) * 3 + 2] : 0.f;
         }
         __syncthreads();
+        }
         const int nblk = min(4, (M - m0 + 15) >> 4);
         // One 16-row block of the tile at a time (unlike conv1x1_gemm_kernel, which runs the four blocks side by side): the
         // block's accumulators are 16 registers instead of 64, its y_prev values (requested before its MFMA loop, consumed
@@ -541,7 +592,13 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int m = m0 + a * 16 + kk * 4 + r;
-                    yv[r] = (live && m < M) ? ogc_ld4(yb + (size_t)m * hw + p0 + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    if constexpr (FIRST > 0) { // (rows beyond M meet zero weights, a wave that is not live zero x0 values)
+                        float w1r[FIRST];
+                        ogc_first_w1_row<FIRST>(w1r, s_w1, m);
+                        yv[r] = ogc_first_row<FIRST>(x0v, w1r);
+                    } else {
+                        yv[r] = (live && m < M) ? ogc_ld4(yb + (size_t)m * hw + p0 + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
                 }
                 v4f acc[4];
 #pragma unroll
@@ -582,7 +639,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                     }
                 }
                 }
-                if (live) {
+                if (live) { // (wave-uniform; m is uniform over the 16 lanes of a DPP row)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int mi = a * 16 + kk * 4 + r, m = m0 + mi; // C/D layout: row (l >> 4) * 4 + r, column l & 15
@@ -597,11 +654,33 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                             float4 o;
                             o.x = fmaf(al, g.x, fmaf(c2, y.x, c3)); o.y = fmaf(al, g.y, fmaf(c2, y.y, c3));
                             o.z = fmaf(al, g.z, fmaf(c2, y.z, c3)); o.w = fmaf(al, g.w, fmaf(c2, y.w, c3));
-                            ogc_st4(outb + (size_t)m * hw + p0 + 4 * j, o);
+                            if constexpr (FIRST > 0) {
+                                float mine = 0.f; // lane j < c0 of the row keeps channel j's sum (every lane of the row holds them all)
+#pragma unroll
+                                for (int c = 0; c < FIRST; ++c) {
+                                    float d = fmaf(o.w, x0v[c].w, fmaf(o.z, x0v[c].z, fmaf(o.y, x0v[c].y, o.x * x0v[c].x)));
+                                    d += ogc_dpp_f32<0xB1>(d);
+                                    d += ogc_dpp_f32<0x4E>(d);
+                                    d += ogc_dpp_f32<0x141>(d);
+                                    d += ogc_dpp_f32<0x140>(d);
+                                    mine = j == c ? d : mine;
+                                }
+                                if (j < first.c0) atomicAdd(&s_dw[m * FC_MAX_C0 + j], mine);
+                            } else {
+                                ogc_st4(outb + (size_t)m * hw + p0 + 4 * j, o);
+                            }
                         }
                     }
                 }
             }
+        }
+    }
+    }
+    if constexpr (FIRST > 0) {
+        __syncthreads();
+        for (int t = threadIdx.x; t < M * first.c0; t += WG_WAVES * OGC_WAVE) {
+            const float v = s_dw[(t / first.c0) * FC_MAX_C0 + t % first.c0];
+            if (v != 0.0f) unsafeAtomicAdd(first.dw1 + t, v);
         }
     }
 }
@@ -810,4 +889,89 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_pooled_h(int b, int cin, int cout, int 
                                                   ogc_bf16_t *grad_prev, ogc_stream_t stream) {
     return dgrad_adjoint_pooled_impl<ogc_bf16>("ogc_conv1x1_dgrad_adjoint_pooled_h", b, cin, cout, hw, relu, nsample, w, y, coef2,
                                                inj, y_prev, pa, pb, coef, grad_prev, stream);
+}
+
+// ---- the same two kernels behind a first convolution whose output was never stored (first_conv.h) ---------------------------
+extern "C" int ogc_conv1x1_wgrad_moments_first(int b, int cin, int cout, int hw, int relu, int c0, const float *x0, const float *w1,
+                                               const float *pa, const float *pb, const float *grad_y, float *moments,
+                                               ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_wgrad_moments_first";
+    const int rc = ogc_first_check(name, b, cin, c0, hw, x0, w1);
+    if (rc != OGC_OK) return rc;
+    OGC_REQUIRE(cout >= 1 && pa && pb && grad_y && moments, "%s: bad shape or null pointer", name);
+    if (((uintptr_t)grad_y & 15) != 0) {
+        ogc_set_error("%s: grad_y must be 16-byte aligned", name);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    OGC_REQUIRE((long long)cout * hw < (1ll << 31), "%s: one sample exceeds 32-bit indexing", name);
+    hipStream_t s = (hipStream_t)stream;
+    if (b == 0) return OGC_OK;
+    if (ogc_zero_async(moments, sizeof(float) * 2 * (size_t)b * cin * cout, s) != hipSuccess) {
+        ogc_set_error("%s: memset failed", name);
+        return OGC_ERR_LAUNCH;
+    }
+    FirstIn first;
+    first.x0 = x0; first.w1 = w1; first.c0 = c0;
+    const int cp = ogc_first_cp(c0);
+    // (at most two 16-column blocks per workgroup: beyond 32 channels of y1 the grid's z dimension walks the column tiles — the
+    // recomputed operand costs registers the <.., 4> forms do not have)
+#define OGC_MLF(A, C)                                                                                                                    \
+    do {                                                                                                                                 \
+        if (cp == 3) moments_launch<A, C, float, 3>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first); \
+        else if (cp == 6) moments_launch<A, C, float, 6>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first); \
+        else moments_launch<A, C, float, 8>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first); \
+    } while (0)
+    if (cout <= 16 && cin <= 16) OGC_MLF(1, 1);
+    else if (cout <= 32 && cin <= 16) OGC_MLF(2, 1);
+    else if (cout <= 32) OGC_MLF(2, 2);
+    else if (cin <= 16) OGC_MLF(4, 1);
+    else OGC_MLF(4, 2);
+#undef OGC_MLF
+    OGC_CHECK_LAUNCH(name);
+    return OGC_OK;
+}
+
+extern "C" int ogc_conv1x1_dgrad_adjoint_first(int b, int cin, int cout, int hw, int relu, int c0, const float *w,
+                                               const float *grad_y, const float *x0, const float *w1, const float *pa,
+                                               const float *pb, const float *coef, float *grad_w1, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_dgrad_adjoint_first";
+    const int rc = ogc_first_check(name, b, cin, c0, hw, x0, w1);
+    if (rc != OGC_OK) return rc;
+    OGC_REQUIRE(cout >= 1 && w && grad_y && pa && pb && coef && grad_w1, "%s: bad shape or null pointer", name);
+    if (cout > 64 || ((uintptr_t)grad_y & 15) != 0) {
+        ogc_set_error("%s: needs cout <= 64 and a 16-byte aligned grad_y (cout=%d)", name, cout);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    OGC_REQUIRE((long long)cout * hw < (1ll << 31) && b <= 65535, "%s: one sample exceeds 32-bit indexing", name);
+    hipStream_t s = (hipStream_t)stream;
+    if (ogc_zero_async(grad_w1, sizeof(float) * (size_t)cin * c0, s) != hipSuccess) {
+        ogc_set_error("%s: memset failed", name);
+        return OGC_ERR_LAUNCH;
+    }
+    if (b == 0) return OGC_OK;
+    const int M = cin, K = cout, Kq = (K + 3) / 4;
+    const size_t lds = ((size_t)64 * ogc_a_ld(Kq) + 64 * 5) * sizeof(float);
+    // ~768 workgroups over the chip (three per CU are resident: one round), each walking a run of consecutive 256-position tiles
+    // of one sample: the atomics per element of dW1 stay in the hundreds
+    const int tiles = ogc_divup(hw, 64 * WG_WAVES);
+    int chunks = 768 / b;
+    if (chunks < 1) chunks = 1;
+    if (chunks > tiles) chunks = tiles;
+    FirstIn first;
+    first.x0 = x0; first.w1 = w1; first.c0 = c0; first.dw1 = grad_w1;
+    first.run = ogc_divup(tiles, chunks);
+    dim3 grid(ogc_divup(tiles, first.run), b);
+    const int cp = ogc_first_cp(c0);
+#define OGC_DGAF(KQV, CPV)                                                                                                  \
+    hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, float, false, CPV>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, \
+                       relu, w, grad_y, (const float *)nullptr, pa, pb, coef, (const float2 *)nullptr, (const float2 *)nullptr, 0, \
+                       (float *)nullptr, first)
+    if (Kq <= 8) {
+        if (cp == 3) OGC_DGAF(8, 3); else if (cp == 6) OGC_DGAF(8, 6); else OGC_DGAF(8, 8);
+    } else {
+        if (cp == 3) OGC_DGAF(16, 3); else if (cp == 6) OGC_DGAF(16, 6); else OGC_DGAF(16, 8);
+    }
+#undef OGC_DGAF
+    OGC_CHECK_LAUNCH(name);
+    return OGC_OK;
 }

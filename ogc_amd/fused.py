@@ -945,6 +945,106 @@ def norm_act_conv(y_prev, stats_prev, gn, relu, conv, next_gn=None, pool=0):
     return res[0], res[1]
 
 
+# ---- the first two layers of a level's MLP as one node: the first convolution's output is never stored -----------------------
+# y1 = conv(x0, W1) of a grouped input with c0 <= 8 channels costs c0 multiply-adds per element to make and a pass over memory
+# each time it is written or read — six such passes per scale of the first level (its own store, the next layer's forward, moment
+# and adjoint kernels, the store of its gradient and the weight-gradient kernel that reads it).  Here every consumer rebuilds
+# the float4 of y1 it would have loaded from x0 and W1 (csrc/first_conv.h: the matrix kernel's rounding, bit for bit), the
+# GroupNorm statistics of y1 come from a pass that stores nothing, and dW1 is summed in the adjoint kernel's epilogue, which
+# holds the gradient with respect to y1 and the x0 values: neither y1 nor its gradient exists in memory.  False: the two nodes
+# (pointwise_conv, _NormActConv), for A/B runs (tools/step_ab.py FIRST_PAIR_FUSED).
+FIRST_PAIR_FUSED = True
+FIRST_PAIR_MAX_C0 = 8
+
+
+class _FirstPairConv(Function):
+    """y2 = conv(act(GroupNorm(conv(x0, W1))), W2) for an input x0 (B, c0 <= 8, ...) that needs no gradient.
+    Returns (y2, statistics of y2 for the next GroupNorm), as _NormActConv does."""
+
+    @staticmethod
+    def forward(ctx, x0, w1, gn_weight, gn_bias, w2, gn_groups, eps, relu, next_groups):
+        ctx.set_materialize_grads(False)
+        nat = _api._native
+        B, c0 = x0.shape[0], x0.shape[1]
+        c1, c2 = w1.shape[0], w2.shape[0]
+        hw = x0.numel() // (B * c0)
+        dev = x0.device
+        slots = nat.conv1x1_gn_slots()
+        w1c, w2c = w1.contiguous(), w2.contiguous()
+        stats1 = zeroed_empty(slots * B * gn_groups * 2, torch.float64, dev)
+        nat.first_conv_stats_wrapper(B, c1, c0, hw, gn_groups, x0, w1c, stats1)
+        mean = torch.empty(B * gn_groups, dtype=torch.float32, device=dev)
+        rstd = torch.empty_like(mean)
+        a = torch.empty(B * c1, dtype=torch.float32, device=dev)
+        bb = torch.empty_like(a)
+        nat.group_norm_coeffs_wrapper(B, c1, hw, gn_groups, eps, None, gn_weight.contiguous(), gn_bias.contiguous(), stats1,
+                                      slots, None, mean, rstd, a, bb)
+        y2 = torch.empty((B, c2) + tuple(x0.shape[2:]), dtype=torch.float32, device=dev)
+        stats2 = zeroed_empty(slots * B * next_groups * 2, torch.float64, dev)
+        nat.conv1x1_gemm_affine_first_wrapper(B, c2, c1, hw, relu, next_groups, c0, w2c, x0, w1c, a, bb, y2, stats2)
+        ctx.save_for_backward(x0, w1, gn_weight, w2, mean, rstd, a, bb)
+        ctx.cfg = (gn_groups, relu, hw)
+        ctx.mark_non_differentiable(stats2)
+        return y2, stats2
+
+    @staticmethod
+    def backward(ctx, grad_y, _grad_stats=None):
+        if grad_y is None:
+            return (None,) * 9
+        nat = _api._native
+        x0, w1, gn_weight, w2, mean, rstd, a, bb = ctx.saved_tensors
+        gn_groups, relu, hw = ctx.cfg
+        B, c0 = x0.shape[0], x0.shape[1]
+        c1, c2 = w1.shape[0], w2.shape[0]
+        dev = x0.device
+        grad_y = grad_y.contiguous()
+        w1c, w2c = w1.contiguous().view(c1, c0), w2.contiguous().view(c2, c1)
+        moments = zeroed_empty((B, 2, c2, c1), torch.float32, dev)
+        nat.conv1x1_wgrad_moments_first_wrapper(B, c1, c2, hw, relu, c0, x0, w1c, a, bb, grad_y, moments)
+        grad_w2 = zeroed_empty((c2, c1), torch.float32, dev)
+        coef = torch.empty(B, c1, 3, dtype=torch.float32, device=dev)
+        ggb = zeroed_empty((2, c1), torch.float32, dev)
+        nat.gn_moments_combine_wrapper(B, c1, c2, hw, gn_groups, moments, w2c, a, bb, mean, rstd, gn_weight.contiguous(),
+                                       grad_w2, coef, ggb[0], ggb[1])
+        grad_w1 = zeroed_empty((c1, c0), torch.float32, dev)
+        nat.conv1x1_dgrad_adjoint_first_wrapper(B, c1, c2, hw, relu, c0, w2c, grad_y, x0, w1c, a, bb, coef, grad_w1)
+        return None, grad_w1.view_as(w1), ggb[0], ggb[1], grad_w2.view_as(w2), None, None, None, None
+
+
+def _plain_conv(conv):
+    return (conv.bias is None and conv.groups == 1 and all(k == 1 for k in conv.kernel_size)
+            and all(v == 1 for v in conv.stride) and all(v == 0 for v in conv.padding))
+
+
+def first_pair_available(x, conv, gn, conv2, gn2):
+    """Can the first two layers of a shared MLP run as _FirstPairConv?  x: the MLP's input; (conv, gn), (conv2, gn2): its first
+    two conv -> GroupNorm blocks, the second a middle layer.  (Not a counted gate: most MLPs do not start on a narrow input.)"""
+    if not FIRST_PAIR_FUSED or deterministic():
+        return False
+    nat = _api._native
+    if (getattr(nat, "conv1x1_dgrad_adjoint_first_wrapper", None) is None or not FUSED_GN_BACKWARD
+            or nat.get_matmul_precision() != "fp32"):
+        return False
+    if not (x is not None and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 3
+            and not x.requires_grad and 1 <= x.shape[1] <= FIRST_PAIR_MAX_C0 and x.shape[0] >= 1):
+        return False
+    if not (_plain_conv(conv) and _plain_conv(conv2) and gn.affine and gn2.affine):
+        return False
+    c0, c1, c2 = x.shape[1], conv.weight.shape[0], conv2.weight.shape[0]
+    hw = x.numel() // (x.shape[0] * c0)
+    g1, g2 = gn.num_groups, gn2.num_groups
+    return (conv.weight.shape[1] == c0 and conv2.weight.shape[1] == c1 and hw % 64 == 0
+            and c1 <= FUSED_GN_BACKWARD_MAX_WIDTH and c2 <= FUSED_GN_BACKWARD_MAX_WIDTH
+            and g1 <= 32 and c1 % g1 == 0 and (c1 // g1) % 4 == 0 and g2 <= 32 and c2 % g2 == 0 and (c2 // g2) % 4 == 0
+            and max(c1, c2) * hw < 2 ** 31 and x.shape[0] <= 32768)
+
+
+def first_pair_conv(x, conv, gn, relu, conv2, gn2):
+    """(y2, statistics of y2 for gn2) = conv2(act(gn(conv(x)))), see _FirstPairConv."""
+    return _FirstPairConv.apply(x, conv.weight, gn.weight, gn.bias, conv2.weight, gn.num_groups, gn.eps, bool(relu),
+                                gn2.num_groups)
+
+
 # The tail of a set-abstraction MLP — last convolution, its GroupNorm / ReLU, the max over the neighbourhood — as ONE autograd
 # node, so that the gradient w.r.t. the convolution's output (the size of the level's widest activation) is never written: it
 # is affine in that output except at one arg-max position per neighbourhood, and the weight- / input-gradient kernels rebuild

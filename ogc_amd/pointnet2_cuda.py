@@ -758,6 +758,29 @@ def conv1x1_dgrad_adjoint_wrapper(b, cin, cout, hw, relu, w, grad_y, y_prev, pa,
          _f(coef, "coef"), op)
 
 
+def first_conv_stats_wrapper(b, c1, c0, hw, groups, x0, w1, stats):
+    """GroupNorm statistics of conv(x0, w1) without its output (ogc_first_conv_stats); stats as conv1x1_gemm_gnstats_wrapper's."""
+    _run("ogc_first_conv_stats", x0, b, c1, c0, hw, groups, _f(x0, "x0"), _f(w1, "w1"), _check(stats, torch.float64, "stats"))
+
+
+def conv1x1_gemm_affine_first_wrapper(b, M, K, hw, relu, groups, c0, w, x0, w1, pa, pb, out, stats):
+    """conv1x1_gemm_affine_wrapper on in = conv(x0, w1), recomputed while loading (ogc_conv1x1_gemm_affine_first)."""
+    _run("ogc_conv1x1_gemm_affine_first", x0, b, M, K, hw, int(relu), groups, c0, _f(w, "w"), _f(x0, "x0"), _f(w1, "w1"),
+         _f(pa, "pa"), _f(pb, "pb"), _f(out, "out"), _check(stats, torch.float64, "stats"))
+
+
+def conv1x1_wgrad_moments_first_wrapper(b, cin, cout, hw, relu, c0, x0, w1, pa, pb, grad_y, moments):
+    _run("ogc_conv1x1_wgrad_moments_first", x0, b, cin, cout, hw, int(relu), c0, _f(x0, "x0"), _f(w1, "w1"), _f(pa, "pa"),
+         _f(pb, "pb"), _f(grad_y, "grad_y"), _f(moments, "moments"))
+
+
+def conv1x1_dgrad_adjoint_first_wrapper(b, cin, cout, hw, relu, c0, w, grad_y, x0, w1, pa, pb, coef, grad_w1):
+    """The adjoint input gradient of the layer behind a first convolution, folded into that convolution's weight gradient
+    grad_w1 (c1, c0) (ogc_conv1x1_dgrad_adjoint_first)."""
+    _run("ogc_conv1x1_dgrad_adjoint_first", x0, b, cin, cout, hw, int(relu), c0, _f(w, "w"), _f(grad_y, "grad_y"), _f(x0, "x0"),
+         _f(w1, "w1"), _f(pa, "pa"), _f(pb, "pb"), _f(coef, "coef"), _f(grad_w1, "grad_w1"))
+
+
 def group_norm_maxpool_bwd_sparse_wrapper(b, c, p, s, groups, relu, x, gamma, mean, rstd, out, argmax, grad_out, coef2, inj,
                                           grad_gamma, grad_beta, ws, x_at_argmax=None):
     """coef2 (b, c, 2), inj (b, c, p, 2): the gradient of the pooled GroupNorm w.r.t. x in sparse form

@@ -187,8 +187,26 @@ def _shared_mlp_run(self, x, pool, first=None):
             return group_norm_act_maxpool(y, gn, relu, stats, extremes)
         return group_norm_act(y, gn, relu, stats)
 
+    def block(layer):
+        conv_name, norm_name, relu = layer._names
+        return getattr(layer, conv_name), getattr(layer, norm_name)[0], relu
+
+    skip = False
     for li, layer in enumerate(layers):
+        if skip:   # the second layer of a first pair: evaluated together with the first
+            skip = False
+            continue
         fusable = isinstance(layer, _ConvNd) and layer._gn_fuse
+        if (fusable and li == 0 and first is None and len(layers) >= 2 + (1 if pool else 0)
+                and isinstance(layers[1], _ConvNd) and layers[1]._gn_fuse):
+            # a narrow input (the grouped coordinates and features of a first level): the first two layers as one node
+            # that never stores the first convolution's output or its gradient (fused._FirstPairConv)
+            from ..fused import first_pair_available, first_pair_conv
+            (conv, gn, relu), (conv2, gn2, relu2) = block(layer), block(layers[1])
+            if first_pair_available(x, conv, gn, conv2, gn2):
+                y, stats = first_pair_conv(x, conv, gn, relu, conv2, gn2)
+                pending, skip = (y, stats, gn2, relu2, None), True
+                continue
         if not fusable:
             if pending is not None:
                 x, pending = flush(pending, False), None
