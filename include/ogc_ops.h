@@ -53,7 +53,7 @@ enum {
  * The supervised mask loss (ogc_sup_loss_ws_doubles, ogc_sup_match_cost, ogc_sup_mask_loss_fwd / _bwd) likewise: new entry points
  * only, and two tests of 0.2.8 pin the number.  ogc_seg_eval_ignore likewise: a new entry point, ogc_seg_eval unchanged.
  * ogc_soft_carry likewise: a new entry point, no prototype changed.  ogc_scan_crop_camera / _front / _tile and ogc_box_segm /
- * _chunk likewise. */
+ * _chunk likewise.  ogc_kittisf_unproject and ogc_png_unfilter likewise. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -591,6 +591,37 @@ int ogc_scan_crop_tile(void); /* OGC_SCAN_CROP_TILE of the library */
 int ogc_box_segm(int n, int k, const float *pc, int sign_x, int sign_y, int sign_z, const double *boxes, const int *ids,
                  int *segm, int *semantic_segm, ogc_stream_t stream);
 int ogc_box_segm_chunk(void); /* OGC_BOX_SEGM_CHUNK of the library */
+
+/* Data preparation, KITTI Scene Flow: disparity and optical-flow maps unprojected to two clouds in correspondence, far and
+ * invalid pixels dropped by a STABLE compaction, instance ids relabelled.  Replaces
+ *   data_prepare/kittisf/process_kittisf.py:43-87, kittisf_util.py:6-27 (pixel2xyz), :59-63 (disp_2_depth), :72-81 (filter_segm)
+ * disp1, disp2, inst (height, width) and flow (height, width, 3) are the 16-bit samples of the four PNGs; fb = focal length *
+ * 0.54 as the caller rounds it to fp32, f = P[0][0], p02 .. p23 the entries of P_rect_02.  Per pixel (row i, column j), fp32,
+ * one rounding per operation, never contracted:
+ *   valid  = d1 > 0 && d2 > 0 && flow[2] == 1
+ *   depthk = fb / (float(dk) / 256 + 1e-5f)                                                          k = 1, 2
+ *   x1 = -((float(j) * (depth1 + p23) - (p02 * depth1 + p03)) / f),  y1 likewise with float(i), p12, p13;  z1 = depth1
+ *   px2 = float(j) + (float(flow[0]) - 32768) / 64,  py2 = float(i) + (float(flow[1]) - 32768) / 64
+ *   x2, y2 as x1, y1 with px2, py2, depth2;  z2 = depth2
+ *   keep = valid && z1 < depth_thresh && z2 < depth_thresh
+ * pc1, pc2 (height * width, 3) f32, segm, keep_idx (height * width,) i32, count (1,) i32, all device memory.  Rows 0 .. count-1
+ * hold the kept pixels IN PIXEL ORDER, keep_idx = i * width + j; rows >= count are not written.  segm: the raw ids (inst) present
+ * AMONG THE KEPT PIXELS whose semantic, id >> 8, is one of the n_select values of select_semantics (device, i32; values outside
+ * 0..255 match nothing) are numbered 1, 2, ... in ascending id order; every other kept pixel gets 0.
+ * Three launches on `stream` (the clearing of a 65 536-bit presence table in the stream's workspace, count, scatter),
+ * OGC_SCAN_CROP_TILE pixels per workgroup, no workgroup waits for another.  height == 0 or width == 0: OGC_OK, count = 0, no
+ * kernel.  height * width beyond 32-bit indexing, n_select outside 0..256, a null pointer (select_semantics may be null when
+ * n_select == 0): OGC_ERR_INVALID_ARG, nothing launched. */
+int ogc_kittisf_unproject(int height, int width, const unsigned short *disp1, const unsigned short *disp2,
+                          const unsigned short *flow, const unsigned short *inst, float fb, float f, float p02, float p03,
+                          float p12, float p13, float p23, float depth_thresh, const int *select_semantics, int n_select,
+                          float *pc1, float *pc2, int *segm, int *keep_idx, int *count, ogc_stream_t stream);
+
+/* The row filters of a PNG undone on the HOST (csrc/png_unfilter.h; no stream, nothing is launched — hence the integers last).
+ * in: the inflated IDAT stream, height rows of (1 filter byte + row_bytes bytes); out: height * row_bytes bytes; bpp the bytes
+ * per complete pixel.  A null pointer, a negative size, bpp not in {1, 2, 3, 6}, row_bytes % bpp != 0, a filter byte above 4:
+ * OGC_ERR_INVALID_ARG with a message. */
+int ogc_png_unfilter(const unsigned char *in, unsigned char *out, int height, int row_bytes, int bpp);
 
 /* Attention core of the MaskFormer head's nn.MultiheadAttention layers
  *   utils/transformer_util.py:5-62 (cross-attention slots <- points, self-attention among the slots; 8 heads,

@@ -87,6 +87,9 @@ SIGNATURES = {
     "ogc_scan_crop_tile": [],
     "ogc_box_segm": [_int, _int, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp],
     "ogc_box_segm_chunk": [],
+    "ogc_kittisf_unproject": [_int, _int, _vp, _vp, _vp, _vp, _flt, _flt, _flt, _flt, _flt, _flt, _flt, _flt, _vp, _int,
+                              _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_png_unfilter": [_vp, _vp, _int, _int, _int],   # host code, no stream: the integers last
     "ogc_group_concat": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_fwd": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_bwd": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],

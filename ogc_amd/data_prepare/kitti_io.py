@@ -37,6 +37,19 @@ def read_semantickitti_calib(path):
     return {"P": c["P2"].reshape(3, 4), "V2C": c["Tr"].reshape(3, 4)}
 
 
+def read_kittisf_calib(path):
+    """KITTI Scene Flow calib_cam_to_cam/%06d.txt -> P_rect_02 as a (3, 4) float32 array (process_kittisf.py:32-40): exactly one
+    such line, and equal focal lengths on both axes."""
+    with open(path) as f:
+        lines = [line for line in f.readlines() if line.startswith("P_rect_02")]
+    if len(lines) != 1:
+        raise ValueError("%s: %d lines start with P_rect_02, expected one" % (path, len(lines)))
+    P = np.array([float(item) for item in lines[0].split()[1:]], dtype=np.float32).reshape(3, 4)
+    if P[0, 0] != P[1, 1]:
+        raise ValueError("%s: P_rect_02 has different focal lengths, %r and %r" % (path, P[0, 0], P[1, 1]))
+    return P
+
+
 def image_size(path):
     """(width, height) from the image's header."""
     from PIL import Image

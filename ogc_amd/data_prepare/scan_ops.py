@@ -1,5 +1,5 @@
-"""The device operators of data preparation (csrc/scan_prepare.hip).  Inputs are CUDA tensors, results stay on the
-device; the only host read is the number of kept points of a crop.  There is no CPU path."""
+"""The device operators of data preparation (csrc/scan_prepare.hip; csrc/kittisf_prepare.hip).  Inputs are
+CUDA tensors, results stay on the device; the only host read is the number of kept points of a crop.  There is no CPU path."""
 import numpy as np
 import torch
 
@@ -89,3 +89,60 @@ def box_segm(pc, boxes, ids, sign=(1, 1, 1)):
     semantic_segm = torch.empty(n, dtype=torch.int32, device=pc.device)
     _native.box_segm_wrapper(n, boxes.shape[0], pc.contiguous(), sign, boxes.contiguous(), ids.contiguous(), segm, semantic_segm)
     return segm, semantic_segm
+
+
+KITTISF_SELECT_SEMANTICS = (26, 28)     # `Car` and `Truck`, the categories process_kittisf.py keeps
+
+
+def _check_maps(maps):
+    """maps: (tensor, name, shape) of the 16-bit maps of one frame.  Types first, so that a wrong dtype is a TypeError whichever
+    map has it and wherever the tensors live."""
+    for t, name, _ in maps:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype != _native.U16:
+            raise TypeError("%s must be %s, got %s" % (name, _native.U16, t.dtype))
+    for t, name, shape in maps:
+        if t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (HIP device); ogc_amd has no CPU path" % name)
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, shape, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise RuntimeError("%s must be contiguous" % name)
+
+
+def kittisf_unproject(disp1, disp2, flow, inst, P_rect, select_semantics=KITTISF_SELECT_SEMANTICS, depth_thresh=35.0):
+    """The two clouds of a KITTI Scene Flow frame (process_kittisf.py:43-87): disp1, disp2, inst (H, W) and flow (H, W, 3), the
+    16-bit samples of the four PNGs as CUDA tensors (torch.uint16; int16 views of the same bits where torch has none), P_rect the
+    (3, 4) float32 numpy array of P_rect_02 -> (pc1 (M, 3) fp32, pc2 (M, 3) fp32, segm (M,) int32, keep_idx (M,) int32 = row *
+    W + column), on the device, in pixel order.  segm numbers the instance ids present among the kept pixels whose semantic
+    (id >> 8) is in select_semantics 1, 2, ... in ascending order; everything else is 0 (kittisf_util.py:72-81)."""
+    if not isinstance(disp1, torch.Tensor):
+        raise TypeError("disp1 must be a torch.Tensor")
+    if disp1.dim() != 2:
+        raise ValueError("disp1 must be (H, W), got %s" % (tuple(disp1.shape),))
+    height, width = disp1.shape
+    _check_maps(((disp1, "disp1", (height, width)), (disp2, "disp2", (height, width)), (flow, "flow", (height, width, 3)),
+                 (inst, "inst", (height, width))))
+    P = np.asarray(P_rect)
+    if P.dtype != np.float32 or P.shape != (3, 4):
+        raise ValueError("P_rect must be a (3, 4) float32 array, got %s %s" % (P.dtype, P.shape))
+    if not (P[0, 1] == 0 and P[1, 0] == 0 and P[2, 0] == 0 and P[2, 1] == 0 and P[0, 0] == P[1, 1]):   # kittisf_util.py:7-11
+        raise ValueError("P_rect must have P[0,1] = P[1,0] = P[2,0] = P[2,1] = 0 and P[0,0] = P[1,1]")
+    select = [int(s) for s in select_semantics]
+    if len(select) > 256:
+        raise ValueError("select_semantics holds %d values, at most 256" % len(select))
+    focal = P[0, 0]
+    fb = np.float32(focal * 0.54)               # FOCAL_LENGTH_PIXEL * BASELINE as the reference writes it (kittisf_util.py:60-61)
+    n = height * width
+    dev = disp1.device
+    pc1 = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    pc2 = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    segm = torch.empty(n, dtype=torch.int32, device=dev)
+    keep_idx = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    sel = torch.tensor(select + [0] * (1 if not select else 0), dtype=torch.int32, device=dev)
+    _native.kittisf_unproject_wrapper(height, width, disp1, disp2, flow, inst, fb, focal, P[0, 2], P[0, 3], P[1, 2], P[1, 3], P[2, 3],
+                                      depth_thresh, sel, len(select), pc1, pc2, segm, keep_idx, count)
+    m = int(count.item())
+    return pc1[:m], pc2[:m], segm[:m], keep_idx[:m]

@@ -433,6 +433,32 @@ def box_segm_wrapper(n, k, pc, sign, boxes, ids, segm, semantic_segm):
          _i(ids, "ids"), _i(segm, "segm"), _i(semantic_segm, "semantic_segm"))
 
 
+U16 = getattr(torch, "uint16", torch.int16)   # the 16-bit samples of a PNG; int16 holds the same bits where torch has no uint16
+
+
+def kittisf_unproject_wrapper(height, width, disp1, disp2, flow, inst, fb, f, p02, p03, p12, p13, p23, depth_thresh,
+                              select_semantics, n_select, pc1, pc2, segm, keep_idx, count):
+    """KITTI-SF maps to two clouds in correspondence as a stable compaction (ogc_kittisf_unproject): disp1, disp2, inst
+    (height, width) and flow (height, width, 3) 16-bit, select_semantics (n_select,) i32 -> rows 0 .. count-1 of pc1, pc2
+    (height * width, 3) f32 and segm, keep_idx (height * width,) i32 in pixel order, count (1,) i32; later rows are not written."""
+    _run("ogc_kittisf_unproject", count, height, width, _check(disp1, U16, "disp1"), _check(disp2, U16, "disp2"),
+         _check(flow, U16, "flow"), _check(inst, U16, "inst"), float(fb), float(f), float(p02), float(p03), float(p12), float(p13),
+         float(p23), float(depth_thresh), _i(select_semantics, "select_semantics"), int(n_select), _f(pc1, "pc1"), _f(pc2, "pc2"),
+         _i(segm, "segm"), _i(keep_idx, "keep_idx"), _i(count, "count"))
+
+
+def png_unfilter(stream_bytes, height, row_bytes, bpp):
+    """The row filters of an inflated PNG stream undone on the host (ogc_png_unfilter; nothing is launched): bytes of
+    height * (1 + row_bytes) -> numpy uint8 (height, row_bytes)."""
+    import numpy as np
+    src = np.frombuffer(stream_bytes, dtype=np.uint8)
+    if src.size != height * (1 + row_bytes):
+        raise ValueError("the stream holds %d bytes, %d rows of 1 + %d bytes need %d" % (src.size, height, row_bytes, height * (1 + row_bytes)))
+    out = np.empty((height, row_bytes), dtype=np.uint8)
+    _lib.call("ogc_png_unfilter", src.ctypes.data, out.ctypes.data, int(height), int(row_bytes), int(bpp))
+    return out
+
+
 def group_concat_wrapper(b, c, n, npoints, nsample, xyz, new_xyz, points, idx, out):
     """out = cat([xyz[idx] - new_xyz, points[idx]], dim=1) (ogc_group_concat); points may be None when c == 0."""
     _run("ogc_group_concat", xyz, b, c, n, npoints, nsample, _f(xyz, "xyz"), _f(new_xyz, "new_xyz"),

@@ -721,3 +721,58 @@ def write_waymo_raw_root(root, n_sequences, n_frames, n_points, seed=9200, data_
     with open(os.path.join(root, split + ".txt"), "w") as f:
         f.write("\n".join(["%s.tfrecord" % n for n in names] + ["segment-absent_with_camera_labels.tfrecord"]) + "\n")
     return out
+
+
+# P_rect_02 of a KITTI Scene Flow calib_cam_to_cam file, as the numbers the file holds
+KITTISF_P_RECT = ((721.5377, 0.0, 609.5593, 44.85728), (0.0, 721.5377, 172.854, 0.2163791), (0.0, 0.0, 1.0, 0.002745884))
+# raw instance ids (semantic * 256 + instance) of the synthetic instance maps: background, two cars (26), a truck (28) — the
+# semantics process_kittisf keeps — and a person (24), a bus (27) and a bicycle (33), which it does not
+KITTISF_INSTANCE_IDS = (0, 26 * 256 + 1, 26 * 256 + 2, 28 * 256 + 1, 24 * 256 + 1, 27 * 256 + 3, 33 * 256)
+
+
+def make_kittisf_maps(height, width, rs):
+    """The four 16-bit maps of one KITTI Scene Flow frame, drawn from the RandomState `rs`: disp1, disp2, inst (H, W) and flow
+    (H, W, 3) uint16.  Disparities between 1500 and 12000 raw (5.9 .. 46.9 px: depths of 66 .. 8.3 m, on both sides of the 35-m
+    threshold) with about 20 % zeros (no ground truth) in each map; flows of up to +-20 px with about 80 % of the validity flags
+    1; the instance map constant on blocks of 8 x 16 pixels with ids of KITTISF_INSTANCE_IDS, half of the blocks background."""
+    import numpy as np
+    disp1 = rs.randint(1500, 12001, size=(height, width))
+    disp2 = np.clip(disp1 + rs.randint(-400, 401, size=(height, width)), 1500, 12000)
+    disp1[rs.rand(height, width) < 0.2] = 0
+    disp2[rs.rand(height, width) < 0.2] = 0
+    flow = np.stack([32768 + rs.randint(-1280, 1281, size=(height, width)), 32768 + rs.randint(-1280, 1281, size=(height, width)),
+                     (rs.rand(height, width) < 0.8).astype(np.int64)], 2)
+    blocks = rs.randint(1, len(KITTISF_INSTANCE_IDS), size=((height + 7) // 8, (width + 15) // 16))
+    blocks[rs.rand(*blocks.shape) < 0.5] = 0
+    inst = np.asarray(KITTISF_INSTANCE_IDS)[np.repeat(np.repeat(blocks, 8, 0), 16, 1)[:height, :width]]
+    return disp1.astype(np.uint16), disp2.astype(np.uint16), flow.astype(np.uint16), inst.astype(np.uint16)
+
+
+def write_kittisf_raw_root(root, n_frames, height=48, width=160, seed=9300):
+    """`n_frames` raw KITTI Scene Flow frames under <root>/training, in the layout of the download: disp_occ_0/%06d_10.png,
+    disp_occ_1/%06d_10.png, instance/%06d_10.png (16-bit grey), flow_occ/%06d_10.png (16-bit RGB) — the maps of
+    make_kittisf_maps, written by data_prepare/png16.py with mixed row filters — and calib_cam_to_cam/%06d.txt — what
+    process_kittisf reads.  Returns a list of frames {"disp1", "disp2", "flow", "inst": the arrays, "P_rect": (3, 4) float32}."""
+    import os
+
+    import numpy as np
+
+    from ..data_prepare.png16 import write_png
+    base = os.path.join(root, "training")
+    for sub in ("disp_occ_0", "disp_occ_1", "flow_occ", "instance", "calib_cam_to_cam"):
+        os.makedirs(os.path.join(base, sub), exist_ok=True)
+    frames = []
+    for i in range(n_frames):
+        rs = np.random.RandomState(seed + i)
+        disp1, disp2, flow, inst = make_kittisf_maps(height, width, rs)
+        for sub, array in (("disp_occ_0", disp1), ("disp_occ_1", disp2), ("flow_occ", flow), ("instance", inst)):
+            write_png(os.path.join(base, sub, "%06d_10.png" % i), array, filters=rs.randint(0, 5, size=height))
+        P = np.asarray(KITTISF_P_RECT, dtype=np.float64)
+        with open(os.path.join(base, "calib_cam_to_cam", "%06d.txt" % i), "w") as f:
+            f.write("calib_time: 09-Jan-2012 13:57:47\ncorner_dist: 9.950000e-02\n")
+            f.write("".join("%s: %s\n" % (key, " ".join("%.6e" % v for v in value.reshape(-1)))
+                            for key, value in (("S_rect_02", np.array([float(width), float(height)])), ("R_rect_02", np.eye(3)),
+                                               ("P_rect_02", P), ("P_rect_03", P))))
+        frames.append({"disp1": disp1, "disp2": disp2, "flow": flow, "inst": inst,
+                       "P_rect": np.array([float("%.6e" % v) for v in P.reshape(-1)], dtype=np.float32).reshape(3, 4)})
+    return frames
