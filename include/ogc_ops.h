@@ -717,6 +717,37 @@ int ogc_conv1x1_dgrad_adjoint_pooled(int b, int cin, int cout, int hw, int relu,
                                      const float *coef2, const float *inj, const float *y_prev, const float *pa,
                                      const float *pb, const float *coef, float *grad_prev, ogc_stream_t stream);
 
+/* The same four kernels of a first level's chain (first pair + pooled tail, fp32) over the LIVE steps of its neighbour lists only.
+ * A list idx (b, p, nsample) ends in repeats of its first entry where the search found fewer than nsample points inside the
+ * radius (utils/pointnet2_util.py:59-79); those columns carry bit-equal values and gradients through the column-wise chain, and
+ * in a sum over positions a weight stands for them.  Per centre, with steps of 16 columns and T = nsample / 16:
+ *     fill = 1 + max{ j : idx[j] != idx[0] } (1: none),   s* = min(fill / 16, T - 1):   steps 0 .. s* are live, the rest skipped;
+ *     when s* < T - 1 the last column of step s* is a repeat and gets the weight 1 + 16 (T - 1 - s*).
+ *   ogc_live_steps: live (b, p * T): per sample the live steps ascending, entry = position / 16, with T - 1 - s* in bits 28 up on
+ *       the entry of step s* (zero on a centre's earlier steps); n_live (b): entries in use.  nsample in {16, 32, 64},
+ *       p <= 32768.  No atomics: the same list in deterministic mode.
+ *   *_live: the entry point without the suffix, summing over the listed steps with those weights: moments, grad_w1 agree with
+ *       the dense form up to fp32 summation order.  ogc_conv1x1_dgrad_adjoint_pooled_live writes grad_prev at the positions of
+ *       live steps ONLY; ogc_conv1x1_wgrad_moments_first_live / _dgrad_adjoint_first_live read grad_y there only.
+ *       nsample in {32, 64}; live_cap (entries per sample of `live`) >= hw / 16, the worst case — n_live stays on the device,
+ *       the grids are sized for that case, and workgroups beyond the list leave at once. */
+int ogc_live_steps(int b, int p, int nsample, const int *idx, int *live, int *n_live, ogc_stream_t stream);
+int ogc_conv1x1_wgrad_moments_pooled_live(int b, int cin, int cout, int hw, int relu, int nsample, const float *y_prev,
+                                          const float *pa, const float *pb, const float *y, const float *coef2,
+                                          const float *inj, const int *live, const int *n_live, int live_cap, float *moments,
+                                          ogc_stream_t stream);
+int ogc_conv1x1_dgrad_adjoint_pooled_live(int b, int cin, int cout, int hw, int relu, int nsample, const float *w, const float *y,
+                                          const float *coef2, const float *inj, const float *y_prev, const float *pa,
+                                          const float *pb, const float *coef, const int *live, const int *n_live, int live_cap,
+                                          float *grad_prev, ogc_stream_t stream);
+int ogc_conv1x1_wgrad_moments_first_live(int b, int cin, int cout, int hw, int relu, int c0, int nsample, const float *x0,
+                                         const float *w1, const float *pa, const float *pb, const float *grad_y,
+                                         const int *live, const int *n_live, int live_cap, float *moments, ogc_stream_t stream);
+int ogc_conv1x1_dgrad_adjoint_first_live(int b, int cin, int cout, int hw, int relu, int c0, int nsample, const float *w,
+                                         const float *grad_y, const float *x0, const float *w1, const float *pa, const float *pb,
+                                         const float *coef, const int *live, const int *n_live, int live_cap, float *grad_w1,
+                                         ogc_stream_t stream);
+
 /* A whole per-neighbourhood MLP and its max-pool in one launch, for INFERENCE
  *   utils/flowstep3d_util.py:57-66 (FlowEmbedding, the correlation layer) and :126-138 (set abstraction):
  *     for conv, bn in zip(mlp_convs, mlp_bns): x = relu(bn(conv(x)));   x = max(x, -1)

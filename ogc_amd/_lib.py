@@ -124,8 +124,17 @@ SIGNATURES = {
                                        _vp, _vp, _vp],
     "ogc_conv1x1_wgrad_moments_pooled": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_conv1x1_dgrad_adjoint_pooled": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_live_steps": [_int, _int, _int, _vp, _vp, _vp, _vp],
+    "ogc_conv1x1_wgrad_moments_pooled_live": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                              _vp],
+    "ogc_conv1x1_dgrad_adjoint_pooled_live": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _int, _vp, _vp],
+    "ogc_conv1x1_wgrad_moments_first_live": [_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                             _vp],
+    "ogc_conv1x1_dgrad_adjoint_first_live": [_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _int, _vp, _vp],
     "ogc_mlp_chain_pool_supported": [_int, _int, _int, _int, _int],
-    "ogc_mlp_chain_pool": [_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_mlp_chain_pool":[_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_corr_layer_pool_supported": [_int, _int, _int, _int, _int],
     "ogc_corr_layer_pool": [_int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp],

@@ -27,6 +27,67 @@
 
 namespace {
 
+// ---- live steps: the 16-position steps of a level's neighbourhoods that hold more than repeats of column 0 ------------------------
+// A neighbour list idx (B, P, S) ends in repeats of its first entry wherever the search found fewer than S points inside the
+// radius (utils/pointnet2_util.py:59-79).  Every kernel of a level's chain is column-wise, so those columns carry bit-equal
+// values and gradients; only sums over positions see them, and there a weight stands for them.  Per centre
+//     fill = 1 + max{ j : idx[j] != idx[0] }  (1: none),   T = S / 16,   s* = min(fill / 16, T - 1):
+// steps 0 .. s* are LIVE, steps s* + 1 .. T - 1 are skipped; when s* < T - 1 the last column of step s* is a repeat (16 (s* + 1) >
+// fill) and stands for itself and the 16 (T - 1 - s*) skipped columns.  The list of a sample: its live steps ascending, entry =
+// position / 16, with the skipped-step count T - 1 - s* in the bits from LIVE_SHIFT up ON THE ENTRY OF STEP s* (zero on the
+// others: the weight 1 + 16 * (entry >> LIVE_SHIFT) belongs to that step's last position alone); n[b] entries of `cap` are used.
+constexpr int LIVE_SHIFT = 28;
+constexpr int LIVE_MASK = (1 << LIVE_SHIFT) - 1;
+struct LiveIn {
+    const int *steps = nullptr; // (B, cap)
+    const int *n = nullptr;     // (B)
+    int cap = 0;
+};
+
+// One workgroup per sample.  Count: a wavefront reads 64 consecutive entries (64 / S whole rows) per load and finds each row's last
+// column that differs from column 0 with a ballot; the centre's live-step count goes to LDS.  Then a run of consecutive centres
+// per thread: sum, scan (as rev_scan_kernel of neighbour_loss.hip), write.
+constexpr int LIVE_MAX_P = 32768; // centres per sample (one byte of LDS each)
+__global__ __launch_bounds__(1024) void live_steps_kernel(int p, int s, const int *__restrict__ idx, int *__restrict__ steps,
+                                                          int *__restrict__ n_live) {
+    __shared__ int part[1024];
+    __shared__ unsigned char cnt[LIVE_MAX_P];
+    const int t = threadIdx.x, b = blockIdx.x, T = s >> 4;
+    const int lane = t & 63, wave = t >> 6;
+    const int *ib = idx + (size_t)b * p * s;
+    int *out = steps + (size_t)b * p * T;
+    const int row0 = lane & ~(s - 1); // the lane of column 0 of this lane's row
+    const unsigned long long row_mask = (s == 64 ? ~0ull : (1ull << s) - 1ull) << row0;
+    const int total = p * s;          // (< 2^31: p <= LIVE_MAX_P, s <= 64)
+    for (int e0 = wave * 64; e0 < total; e0 += 1024) { // (wave-uniform trips; total is a multiple of s, so rows are whole)
+        const bool in = e0 + lane < total;
+        const int v = in ? ib[e0 + lane] : 0;
+        const int first = __shfl(v, row0);
+        const unsigned long long differs = __builtin_amdgcn_ballot_w64(in && v != first) & row_mask;
+        const int hi = differs ? 63 - __clzll(differs) - row0 : 0; // the last column that differs from column 0 (0: none)
+        if (in && lane == row0) cnt[(e0 + lane) / s] = (unsigned char)(min((hi + 1) >> 4, T - 1) + 1); // s* + 1
+    }
+    __syncthreads();
+    const int per = (p + 1023) / 1024;
+    const int c0 = min(t * per, p), c1 = min(c0 + per, p);
+    int sum = 0;
+    for (int c = c0; c < c1; ++c) sum += cnt[c];
+    part[t] = sum;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = t >= off ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int at = t > 0 ? part[t - 1] : 0;
+    for (int c = c0; c < c1; ++c) {
+        const int sl = cnt[c] - 1;
+        for (int st = 0; st <= sl; ++st) out[at++] = (c * T + st) | (st == sl ? (T - 1 - sl) << LIVE_SHIFT : 0);
+    }
+    if (t == 1023) n_live[b] = part[1023];
+}
+
 // ---- moment matrices ------------------------------------------------------------------------------------------------
 // Same operand layout as conv1x1_wgrad_kernel: for a step of 16 positions lane (i = l & 15, k = l >> 4) loads ONE float4 =
 // row (c0 + i), positions pb + 4k .. 4k+3; MFMA k-slot k of sub-step s is position pb + 4k + s for both operands.
@@ -37,7 +98,10 @@ namespace {
 // AT: element type of x and dy (float / ogc_bf16: act_io.h).
 // FIRST (0: off, else the CP of first_conv.h): x is the output of a first convolution that was never stored; a lane rebuilds its
 // CIB float4 of it from the x0 values at its four positions (loaded in x's place) and the rows of W1 it holds in registers.
-template <int COB, int CIB, bool POOLED, typename AT = float, int FIRST = 0>
+// LIST: the wave walks entries of the sample's live-step list (LiveIn above) instead of consecutive steps, its share derived
+// from the list's length so that the live steps spread over all workgroups of the sample; the g_y operand of an entry's last
+// position is multiplied by the entry's weight (the skipped repeats of that column).
+template <int COB, int CIB, bool POOLED, typename AT = float, int FIRST = 0, bool LIST = false>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int cin, int cout, int hw, int chunks,
                                                                            int steps_per_wave, int relu,
                                                                            const AT *__restrict__ x,   // y_prev (B, cin, hw)
@@ -48,14 +112,22 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
                                                                            const float2 *__restrict__ inj,   // (B, cout, hw >> s_shift)
                                                                            int s_shift,
                                                                            float *__restrict__ hm,        // (B, 2, cout, cin)
-                                                                           FirstIn first = FirstIn()) {
+                                                                           FirstIn first = FirstIn(), LiveIn ls = LiveIn()) {
     constexpr int XN = FIRST ? FIRST : CIB; // float4 a lane loads per step in x's place
     __shared__ float red[WG_WAVES][COB * CIB * 256]; // one slab per wave (see conv1x1_wgrad_kernel), H then H2
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i = lane & 15, k = lane >> 4;
     const int img = blockIdx.x / chunks, chunk = blockIdx.x - img * chunks;
     const int co0 = blockIdx.y * (16 * COB), ci0 = blockIdx.z * (16 * CIB);
-    const int steps_per_img = hw >> 4;
+    int steps_per_img = hw >> 4;
+    const int *lv_ = nullptr;
+    if constexpr (LIST) {
+        steps_per_img = min(ls.n[img], ls.cap); // entries of the list (>= 1: every centre keeps its first step)
+        lv_ = ls.steps + (size_t)img * ls.cap;
+        const int waves = chunks * WG_WAVES;
+        steps_per_wave = ((steps_per_img + waves - 1) / waves + 1) & ~1;
+        if (chunk * WG_WAVES * steps_per_wave >= steps_per_img) return; // (the whole workgroup, ahead of every barrier)
+    }
     const int first_step = (chunk * WG_WAVES + wave) * steps_per_wave;
     const int mine = max(0, min(steps_per_wave, steps_per_img - first_step)); // this wavefront's steps: [first_step, first_step + mine)
 
@@ -107,8 +179,10 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
     // for ALL outstanding loads wherever it needs one, which serialises the ping-pong): rows beyond the tensors are clamped
     // onto the last row — they only reach rows / columns of H, H2 that are never stored — and steps beyond the wave's
     // share re-read its last step and are not computed with.
-    auto load = [&](float4(&yv)[COB], float4(&xv)[XN], float2(&jv)[COB], int &jpos) { // step `cur`, then advance
-        const int pb = cur * 16;
+    int ent = LIST ? lv_[cur] : 0; // LIST: the entry of step `cur` (wave-uniform), fetched one step ahead of its loads
+    auto load = [&](float4(&yv)[COB], float4(&xv)[XN], float2(&jv)[COB], int &jpos, int &went) { // step `cur`, then advance
+        const int pb = LIST ? min(ent & LIVE_MASK, (hw >> 4) - 1) * 16 : cur * 16;
+        if constexpr (LIST) went = ent; // (wave-uniform: the weight is formed where it is used)
 #pragma unroll
         for (int a = 0; a < COB; ++a) yv[a] = ogc_ld4(yb_ + yrow[a] + pb);
 #pragma unroll
@@ -119,11 +193,17 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
             jpos = (pb & smask) + 4 * k; // this lane's first position inside the neighbourhood
         }
         cur = min(cur + 1, max(stop, 0));
+        if constexpr (LIST) ent = lv_[cur];
     };
-    auto fma16 = [&](float4(&yv)[COB], const float4(&xraw)[XN], const float2(&jv)[COB], int jpos) {
+    auto fma16 = [&](float4(&yv)[COB], const float4(&xraw)[XN], const float2(&jv)[COB], int jpos, int went) {
         if (POOLED) {
 #pragma unroll
             for (int a = 0; a < COB; ++a) ogc_pooled_grad(yv[a], pc2[a], pc3[a], jv[a], jpos); // (gn_maxpool_bwd_dx_kernel's expression)
+        }
+        if constexpr (LIST) { // the step's last position: lane group k == 3, component .w
+            const float wl = k == 3 ? (float)(1 + 16 * (went >> LIVE_SHIFT)) : 1.f;
+#pragma unroll
+            for (int a = 0; a < COB; ++a) yv[a].w *= wl;
         }
         float4 x0v[FIRST ? FIRST : 1];
         if constexpr (FIRST > 0) {
@@ -163,15 +243,16 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
     float4 ya[COB], xa[XN], yb[COB], xb[XN];
     float2 ja[COB], jb[COB];
     int pa_ = 0, pb_ = 0;
-    load(ya, xa, ja, pa_);
+    int wa_ = 0, wb_ = 0;
+    load(ya, xa, ja, pa_, wa_);
     int s = 0;
     for (; s + 1 < mine; s += 2) { // ping-pong registers: next step's loads fly during the MFMAs (no branch in the body)
-        load(yb, xb, jb, pb_);
-        fma16(ya, xa, ja, pa_);
-        load(ya, xa, ja, pa_);
-        fma16(yb, xb, jb, pb_);
+        load(yb, xb, jb, pb_, wb_);
+        fma16(ya, xa, ja, pa_, wa_);
+        load(ya, xa, ja, pa_, wa_);
+        fma16(yb, xb, jb, pb_, wb_);
     }
-    if (s < mine) fma16(ya, xa, ja, pa_);
+    if (s < mine) fma16(ya, xa, ja, pa_, wa_);
 
     float *dst = hm + (size_t)img * 2 * cout * cin;
 #pragma unroll
@@ -353,7 +434,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments16_kernel(int
 template <int COB, int CIB, typename AT, int FIRST = 0>
 void moments_launch(int b, int cin, int cout, int hw, int relu, const AT *x, const AT *dy, const float *pa,
                     const float *pb, const float *coef2, const float *inj, int s_shift, float *hm, hipStream_t s,
-                    FirstIn first = FirstIn()) {
+                    FirstIn first = FirstIn(), LiveIn ls = LiveIn()) {
     const int steps_per_img = sizeof(AT) == 2 ? hw >> 5 : hw >> 4; // (16-bit tensors: 32 positions per step)
     const int tiles = ogc_divup(cout, 16 * COB) * ogc_divup(cin, 16 * CIB);
     long long waves = (2048 / tiles) / b;            // wavefronts per sample and tile pair: ~2048 over the chip
@@ -372,10 +453,17 @@ void moments_launch(int b, int cin, int cout, int hw, int relu, const AT *x, con
             hipLaunchKernelGGL((wgrad_moments16_kernel<COB, CIB, false>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
                                chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm);
     } else if constexpr (FIRST > 0) {
-        hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT, FIRST>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
-                           chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm, first);
+        if (ls.steps) // (grid of the worst case: every step live; the kernel derives its share from the list's length)
+            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT, FIRST, true>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout,
+                               hw, chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm, first, ls);
+        else
+            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT, FIRST>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
+                               chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm, first, ls);
     } else {
-        if (inj)
+        if (inj && ls.steps)
+            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, true, AT, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
+                               chunks, spw, relu, x, dy, pa, pb, c2, ij, s_shift, hm, first, ls);
+        else if (inj)
             hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, true, AT>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw, chunks,
                                spw, relu, x, dy, pa, pb, c2, ij, s_shift, hm);
         else
@@ -471,7 +559,11 @@ __global__ __launch_bounds__(256) void moments_combine_kernel(int b, int cin, in
 // the weight gradient of that convolution, dW1[m][c] = sum_p g_prev[m][p] x0[c][p], which the epilogue forms from the four
 // positions it holds: summed over the 16 lanes of a DPP row, then over the workgroup's run of first.run position tiles in LDS,
 // then one fp32 atomic per element and workgroup into first.dw1.
-template <int KQ, bool POOLED, typename AT = float, bool BF = false, int FIRST = 0>
+// LIST (fp32, POOLED or FIRST): a wave's tile is FOUR ENTRIES of the sample's live-step list (LiveIn above) instead of 64
+// consecutive positions — lane j holds positions 4 (j & 3) .. + 3 of entry 4 tile + (j >> 2); the geometry of S = 16, four
+// neighbourhoods per tile, and the pooled table is sized for it.  POOLED writes g_prev at live positions only; FIRST multiplies
+// the term of an entry's last position by the entry's weight and derives the workgroup's run of tiles from the list's length.
+template <int KQ, bool POOLED, typename AT = float, bool BF = false, int FIRST = 0, bool LIST = false>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M, int K, int hw, int relu,
                                                                            const float *__restrict__ w,     // (K, M)
                                                                            const AT *__restrict__ gy,    // (B, K, hw)
@@ -483,7 +575,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                                                                            const float2 *__restrict__ inj,   // (B, K, hw >> s_shift)
                                                                            int s_shift,
                                                                            AT *__restrict__ out,         // (B, M, hw)
-                                                                           FirstIn first = FirstIn()) {
+                                                                           FirstIn first = FirstIn(), LiveIn ls = LiveIn()) {
     extern __shared__ __attribute__((aligned(16))) float a_lds[]; // [64][ogc_a_ld(Kq)] weights (conv_stage.h), then [64][5] coefficients
     __shared__ __attribute__((aligned(16))) float s_w1[FIRST ? FC_MAX_ROWS * FC_MAX_C0 : 4]; // FIRST: W1, zero-padded
     __shared__ float s_dw[FIRST ? FC_MAX_ROWS * FC_MAX_C0 : 4];                              // FIRST: the workgroup's share of dW1
@@ -496,41 +588,69 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
     const AT *yb = yprev + (size_t)b * M * hw;
     const int a_ld = ogc_a_ld(Kq);
     float *cf = a_lds + (size_t)64 * a_ld;
+    int run = FIRST ? first.run : 1; // position tiles of 256 a workgroup walks (one, unless FIRST)
+    int n_lv = 0;
+    const int *lv_ = nullptr;
+    if constexpr (LIST) {
+        static_assert((POOLED || FIRST > 0) && !BF && sizeof(AT) == 4, "list form: pooled or first-layer, fp32");
+        n_lv = min(ls.n[b], ls.cap);
+        lv_ = ls.steps + (size_t)b * ls.cap;
+        const int tiles = (n_lv + 4 * WG_WAVES - 1) / (4 * WG_WAVES); // a workgroup's tile: 16 entries
+        if (FIRST) run = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;
+        if ((int)blockIdx.x * run >= tiles) return; // (the whole workgroup, ahead of every barrier)
+    }
     if constexpr (FIRST > 0) { // (visible to all after the barriers in front of the first tile's MFMAs)
         static_assert(!POOLED && !BF && sizeof(AT) == 4, "first-layer form: dense, fp32");
         ogc_first_stage_w1<WG_WAVES * OGC_WAVE>(s_w1, first.w1, M, first.c0);
         for (int t = threadIdx.x; t < FC_MAX_ROWS * FC_MAX_C0; t += WG_WAVES * OGC_WAVE) s_dw[t] = 0.f;
     }
-    const int run = FIRST ? first.run : 1; // position tiles of 256 a workgroup walks (one, unless FIRST)
     for (int it = 0; it < run; ++it) {
-    const int p0 = ((blockIdx.x * run + it) * WG_WAVES + wave) * 64;
-    const bool live = p0 < hw;
+    const int tw = (blockIdx.x * run + it) * WG_WAVES + wave; // the wave's tile
+    const int p0 = tw * 64;
+    const bool live = LIST ? 4 * tw < n_lv : p0 < hw;
+    int pos = p0 + 4 * j; // the lane's first position
+    bool mine_ok = true;  // LIST: the lane's entry exists (the last tile of a list may hold fewer than four)
+    float wl = 1.f;       // LIST: the weight of the lane's LAST position (.w)
+    if constexpr (LIST) {
+        const int q = 4 * tw + (j >> 2);
+        mine_ok = q < n_lv;
+        const int ent = lv_[min(q, n_lv - 1)];
+        pos = min(ent & LIVE_MASK, (hw >> 4) - 1) * 16 + 4 * (j & 3);
+        wl = (j & 3) == 3 ? (float)(1 + 16 * (ent >> LIVE_SHIFT)) : 1.f;
+    }
+    const bool lane_live = live && mine_ok;
     float4 x0v[FIRST ? FIRST : 1];
     if constexpr (FIRST > 0) {
-        ogc_first_load_raw<FIRST>(x0v, first.x0 + (size_t)b * first.c0 * hw + (live ? p0 + 4 * j : 0), first.c0, hw);
-        ogc_first_mask<FIRST>(x0v, first.c0, live);
+        ogc_first_load_raw<FIRST>(x0v, first.x0 + (size_t)b * first.c0 * hw + (live ? pos : 0), first.c0, hw);
+        ogc_first_mask<FIRST>(x0v, first.c0, lane_live);
     }
 
     float4 xin[KQ];
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
         const int row = q * 4 + kk;
-        xin[q] = (live && q < Kq && row < K) ? ogc_ld4(inb + (size_t)row * hw + p0 + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+        xin[q] = (lane_live && q < Kq && row < K) ? ogc_ld4(inb + (size_t)row * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if (POOLED) {
         // (c2, c3, ag, arg) of the wave's K rows x (64 >> s_shift) neighbourhoods through a wave-private LDS table: read back one
         // 16-byte entry per row right where it is used (held in registers next to the K x 64 tile they cost a wavefront per SIMD)
-        const int centres = hw >> s_shift, cpw = 64 >> s_shift;
+        const int centres = hw >> s_shift, cpw = LIST ? 4 : 64 >> s_shift; // LIST: one table column per entry of the tile
         float4 *tab = reinterpret_cast<float4 *>(cf + 64 * 5) + (size_t)wave * K * cpw;
         for (int e = lane; e < K * cpw; e += OGC_WAVE) {
-            const int row = e / cpw, centre = (p0 >> s_shift) + (e - row * cpw);
+            const int row = e / cpw;
+            int centre = (p0 >> s_shift) + (e - row * cpw);
+            if constexpr (LIST) {
+                const int q = 4 * tw + (e - row * cpw);
+                const int step = min(lv_[min(q, n_lv - 1)] & LIVE_MASK, (hw >> 4) - 1);
+                centre = q < n_lv ? (step * 16) >> s_shift : centres;
+            }
             const float2 cc = coef2[(size_t)b * K + row];
             const float2 jj = (live && centre < centres) ? inj[((size_t)b * K + row) * centres + centre]
                                                          : make_float2(0.f, __int_as_float(-1));
             tab[e] = make_float4(cc.x, cc.y, jj.x, jj.y);
         }
         __syncthreads();
-        const int mine = (4 * j) >> s_shift, jpos = (p0 + 4 * j) & ((1 << s_shift) - 1);
+        const int mine = LIST ? j >> 2 : (4 * j) >> s_shift, jpos = pos & ((1 << s_shift) - 1);
 #pragma unroll
         for (int q = 0; q < KQ; ++q) { // the expression of gn_maxpool_bwd_dx_kernel, bit for bit (rows beyond K stay zero)
             const int row = q * 4 + kk;
@@ -597,7 +717,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                         ogc_first_w1_row<FIRST>(w1r, s_w1, m);
                         yv[r] = ogc_first_row<FIRST>(x0v, w1r);
                     } else {
-                        yv[r] = (live && m < M) ? ogc_ld4(yb + (size_t)m * hw + p0 + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        yv[r] = (live && m < M) ? ogc_ld4(yb + (size_t)m * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
                     }
                 }
                 v4f acc[4];
@@ -656,6 +776,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                             o.z = fmaf(al, g.z, fmaf(c2, y.z, c3)); o.w = fmaf(al, g.w, fmaf(c2, y.w, c3));
                             if constexpr (FIRST > 0) {
                                 float mine = 0.f; // lane j < c0 of the row keeps channel j's sum (every lane of the row holds them all)
+                                if constexpr (LIST) o.w *= wl; // (a lane without an entry holds zeros in x0v)
 #pragma unroll
                                 for (int c = 0; c < FIRST; ++c) {
                                     float d = fmaf(o.w, x0v[c].w, fmaf(o.z, x0v[c].z, fmaf(o.y, x0v[c].y, o.x * x0v[c].x)));
@@ -667,7 +788,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                                 }
                                 if (j < first.c0) atomicAdd(&s_dw[m * FC_MAX_C0 + j], mine);
                             } else {
-                                ogc_st4(outb + (size_t)m * hw + p0 + 4 * j, o);
+                                if (mine_ok) ogc_st4(outb + (size_t)m * hw + pos, o);
                             }
                         }
                     }
@@ -690,10 +811,24 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
 namespace {
 int nsample_shift(int nsample) { return nsample == 16 ? 4 : nsample == 32 ? 5 : nsample == 64 ? 6 : -1; }
 
+// the list forms' own preconditions (checked ahead of every launch and memset): a list with room for the worst case, every step
+// live — n_live stays on the device, so a list shorter than that could be shorter than n_live — and S = 32 or 64
+int live_check(const char *name, const int *live, const int *n_live, int live_cap, int hw, int nsample, LiveIn &ls) {
+    OGC_REQUIRE(live && n_live, "%s: null live-step list", name);
+    if (nsample != 32 && nsample != 64) {
+        ogc_set_error("%s: the list form needs nsample 32 or 64 (nsample=%d)", name, nsample);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    OGC_REQUIRE(hw >= 16 && hw % nsample == 0 && (hw >> 4) <= LIVE_MASK && live_cap >= (hw >> 4),
+                "%s: the live-step list holds %d entries per sample, hw=%d needs room for %d", name, live_cap, hw, hw >> 4);
+    ls.steps = live; ls.n = n_live; ls.cap = live_cap;
+    return OGC_OK;
+}
+
 template <typename AT>
 int wgrad_moments_impl(const char *name, int b, int cin, int cout, int hw, int relu, const AT *y_prev, const float *pa,
                        const float *pb, const AT *grad_y, const float *coef2, const float *inj, int s_shift,
-                       float *moments, ogc_stream_t stream) {
+                       float *moments, ogc_stream_t stream, LiveIn ls = LiveIn()) {
     OGC_REQUIRE(b >= 0 && cin >= 1 && cout >= 1 && hw >= 1, "%s: bad shape", name);
     OGC_REQUIRE(y_prev && pa && pb && grad_y && moments, "%s: null pointer", name);
     if ((hw & (sizeof(AT) == 2 ? 31 : 15)) != 0 || (((uintptr_t)y_prev | (uintptr_t)grad_y) & 15) != 0) {
@@ -712,7 +847,7 @@ int wgrad_moments_impl(const char *name, int b, int cin, int cout, int hw, int r
         ogc_set_error("%s: memset failed", name);
         return OGC_ERR_LAUNCH;
     }
-#define OGC_ML(A, C) moments_launch<A, C, AT>(b, cin, cout, hw, relu, y_prev, grad_y, pa, pb, coef2, inj, s_shift, moments, s)
+#define OGC_ML(A, C) moments_launch<A, C, AT>(b, cin, cout, hw, relu, y_prev, grad_y, pa, pb, coef2, inj, s_shift, moments, s, FirstIn(), ls)
     if (cout <= 16 && cin <= 16) OGC_ML(1, 1);
     else if (cout <= 32 && cin <= 16) OGC_ML(2, 1);
     else if (cout <= 32 && cin <= 32) OGC_ML(2, 2);
@@ -745,14 +880,14 @@ namespace {
 template <typename AT>
 int wgrad_moments_pooled_impl(const char *name, int b, int cin, int cout, int hw, int relu, int nsample, const AT *y_prev,
                               const float *pa, const float *pb, const AT *y, const float *coef2, const float *inj,
-                              float *moments, ogc_stream_t stream) {
+                              float *moments, ogc_stream_t stream, LiveIn ls = LiveIn()) {
     const int sh = nsample_shift(nsample);
     if (sh < 0 || hw % nsample != 0 || (((uintptr_t)coef2 | (uintptr_t)inj) & 7) != 0) {
         ogc_set_error("%s: nsample=%d must be 16, 32 or 64 and divide hw=%d", name, nsample, hw);
         return OGC_ERR_UNSUPPORTED;
     }
     OGC_REQUIRE(b == 0 || (coef2 && inj), "%s: null pointer", name);
-    return wgrad_moments_impl<AT>(name, b, cin, cout, hw, relu, y_prev, pa, pb, y, coef2, inj, sh, moments, stream);
+    return wgrad_moments_impl<AT>(name, b, cin, cout, hw, relu, y_prev, pa, pb, y, coef2, inj, sh, moments, stream, ls);
 }
 } // namespace
 
@@ -761,6 +896,17 @@ extern "C" int ogc_conv1x1_wgrad_moments_pooled(int b, int cin, int cout, int hw
                                                 const float *inj, float *moments, ogc_stream_t stream) {
     return wgrad_moments_pooled_impl<float>("ogc_conv1x1_wgrad_moments_pooled", b, cin, cout, hw, relu, nsample, y_prev, pa, pb, y,
                                             coef2, inj, moments, stream);
+}
+
+extern "C" int ogc_conv1x1_wgrad_moments_pooled_live(int b, int cin, int cout, int hw, int relu, int nsample, const float *y_prev,
+                                                     const float *pa, const float *pb, const float *y, const float *coef2,
+                                                     const float *inj, const int *live, const int *n_live, int live_cap,
+                                                     float *moments, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_wgrad_moments_pooled_live";
+    LiveIn ls;
+    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    if (rc != OGC_OK) return rc;
+    return wgrad_moments_pooled_impl<float>(name, b, cin, cout, hw, relu, nsample, y_prev, pa, pb, y, coef2, inj, moments, stream, ls);
 }
 
 extern "C" int ogc_conv1x1_wgrad_moments_pooled_h(int b, int cin, int cout, int hw, int relu, int nsample,
@@ -794,7 +940,7 @@ namespace {
 template <typename AT>
 int dgrad_adjoint_impl(const char *name, int b, int cin, int cout, int hw, int relu, const float *w, const AT *grad_y,
                        const AT *y_prev, const float *pa, const float *pb, const float *coef, const float *coef2,
-                       const float *inj, int s_shift, AT *grad_prev, ogc_stream_t stream) {
+                       const float *inj, int s_shift, AT *grad_prev, ogc_stream_t stream, LiveIn ls = LiveIn()) {
     OGC_REQUIRE(b >= 0 && cin >= 1 && cout >= 1 && hw >= 1, "%s: bad shape", name);
     OGC_REQUIRE(w && grad_y && y_prev && pa && pb && coef && grad_prev, "%s: null pointer", name);
     if ((hw & 63) != 0 || cout > 160 || (((uintptr_t)grad_y | (uintptr_t)y_prev | (uintptr_t)grad_prev) & ogc_act_mask<AT>()) != 0) {
@@ -806,7 +952,7 @@ int dgrad_adjoint_impl(const char *name, int b, int cin, int cout, int hw, int r
     if (b == 0) return OGC_OK;
     const int M = cin, K = cout, Kq = (K + 3) / 4;
     const size_t lds = ((size_t)64 * ogc_a_ld(Kq) + 64 * 5) * sizeof(float) +
-                       (inj ? (size_t)WG_WAVES * K * (64 >> s_shift) * sizeof(float4) : 0);
+                       (inj ? (size_t)WG_WAVES * K * (ls.steps ? 4 : 64 >> s_shift) * sizeof(float4) : 0);
     if (sizeof(AT) == 2 && !ogc_g_matmul_bf16) {
         ogc_set_error("%s: 16-bit activations need ogc_set_matmul_precision(1)", name);
         return OGC_ERR_UNSUPPORTED;
@@ -827,6 +973,13 @@ int dgrad_adjoint_impl(const char *name, int b, int cin, int cout, int hw, int r
     const float2 *c2 = reinterpret_cast<const float2 *>(coef2), *ij = reinterpret_cast<const float2 *>(inj);
 #define OGC_DGA(KQV)                                                                                                        \
     do {                                                                                                                    \
+        if constexpr (sizeof(AT) == 4) {                                                                                    \
+            if (inj && ls.steps) { /* (grid of the worst case; workgroups beyond the list leave at once) */                \
+                hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, true, AT, false, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, \
+                                   hw, relu, w, grad_y, y_prev, pa, pb, coef, c2, ij, s_shift, grad_prev, FirstIn(), ls);  \
+                break;                                                                                                      \
+            }                                                                                                               \
+        }                                                                                                                   \
         if (inj)                                                                                                            \
             hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, true, AT, sizeof(AT) == 2>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, relu, w,  \
                                grad_y, y_prev, pa, pb, coef, c2, ij, s_shift, grad_prev);                                  \
@@ -864,14 +1017,14 @@ namespace {
 template <typename AT>
 int dgrad_adjoint_pooled_impl(const char *name, int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
                               const AT *y, const float *coef2, const float *inj, const AT *y_prev, const float *pa,
-                              const float *pb, const float *coef, AT *grad_prev, ogc_stream_t stream) {
+                              const float *pb, const float *coef, AT *grad_prev, ogc_stream_t stream, LiveIn ls = LiveIn()) {
     const int sh = nsample_shift(nsample);
     if (sh < 0 || hw % nsample != 0 || (((uintptr_t)coef2 | (uintptr_t)inj) & 7) != 0) {
         ogc_set_error("%s: nsample=%d must be 16, 32 or 64 and divide hw=%d", name, nsample, hw);
         return OGC_ERR_UNSUPPORTED;
     }
     OGC_REQUIRE(b == 0 || (coef2 && inj), "%s: null pointer", name);
-    return dgrad_adjoint_impl<AT>(name, b, cin, cout, hw, relu, w, y, y_prev, pa, pb, coef, coef2, inj, sh, grad_prev, stream);
+    return dgrad_adjoint_impl<AT>(name, b, cin, cout, hw, relu, w, y, y_prev, pa, pb, coef, coef2, inj, sh, grad_prev, stream, ls);
 }
 } // namespace
 
@@ -883,6 +1036,18 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_pooled(int b, int cin, int cout, int hw
                                             y_prev, pa, pb, coef, grad_prev, stream);
 }
 
+extern "C" int ogc_conv1x1_dgrad_adjoint_pooled_live(int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
+                                                     const float *y, const float *coef2, const float *inj, const float *y_prev,
+                                                     const float *pa, const float *pb, const float *coef, const int *live,
+                                                     const int *n_live, int live_cap, float *grad_prev, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_dgrad_adjoint_pooled_live";
+    LiveIn ls;
+    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    if (rc != OGC_OK) return rc;
+    return dgrad_adjoint_pooled_impl<float>(name, b, cin, cout, hw, relu, nsample, w, y, coef2, inj, y_prev, pa, pb, coef, grad_prev,
+                                            stream, ls);
+}
+
 extern "C" int ogc_conv1x1_dgrad_adjoint_pooled_h(int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
                                                   const ogc_bf16_t *y, const float *coef2, const float *inj,
                                                   const ogc_bf16_t *y_prev, const float *pa, const float *pb, const float *coef,
@@ -892,10 +1057,10 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_pooled_h(int b, int cin, int cout, int 
 }
 
 // ---- the same two kernels behind a first convolution whose output was never stored (first_conv.h) ---------------------------
-extern "C" int ogc_conv1x1_wgrad_moments_first(int b, int cin, int cout, int hw, int relu, int c0, const float *x0, const float *w1,
-                                               const float *pa, const float *pb, const float *grad_y, float *moments,
-                                               ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_wgrad_moments_first";
+namespace {
+int wgrad_moments_first_impl(const char *name, int b, int cin, int cout, int hw, int relu, int c0, const float *x0, const float *w1,
+                             const float *pa, const float *pb, const float *grad_y, float *moments, ogc_stream_t stream,
+                             LiveIn ls = LiveIn()) {
     const int rc = ogc_first_check(name, b, cin, c0, hw, x0, w1);
     if (rc != OGC_OK) return rc;
     OGC_REQUIRE(cout >= 1 && pa && pb && grad_y && moments, "%s: bad shape or null pointer", name);
@@ -917,9 +1082,9 @@ extern "C" int ogc_conv1x1_wgrad_moments_first(int b, int cin, int cout, int hw,
     // recomputed operand costs registers the <.., 4> forms do not have)
 #define OGC_MLF(A, C)                                                                                                                    \
     do {                                                                                                                                 \
-        if (cp == 3) moments_launch<A, C, float, 3>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first); \
-        else if (cp == 6) moments_launch<A, C, float, 6>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first); \
-        else moments_launch<A, C, float, 8>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first); \
+        if (cp == 3) moments_launch<A, C, float, 3>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first, ls); \
+        else if (cp == 6) moments_launch<A, C, float, 6>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first, ls); \
+        else moments_launch<A, C, float, 8>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first, ls); \
     } while (0)
     if (cout <= 16 && cin <= 16) OGC_MLF(1, 1);
     else if (cout <= 32 && cin <= 16) OGC_MLF(2, 1);
@@ -931,10 +1096,9 @@ extern "C" int ogc_conv1x1_wgrad_moments_first(int b, int cin, int cout, int hw,
     return OGC_OK;
 }
 
-extern "C" int ogc_conv1x1_dgrad_adjoint_first(int b, int cin, int cout, int hw, int relu, int c0, const float *w,
-                                               const float *grad_y, const float *x0, const float *w1, const float *pa,
-                                               const float *pb, const float *coef, float *grad_w1, ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_dgrad_adjoint_first";
+int dgrad_adjoint_first_impl(const char *name, int b, int cin, int cout, int hw, int relu, int c0, const float *w,
+                             const float *grad_y, const float *x0, const float *w1, const float *pa, const float *pb,
+                             const float *coef, float *grad_w1, ogc_stream_t stream, LiveIn ls = LiveIn()) {
     const int rc = ogc_first_check(name, b, cin, c0, hw, x0, w1);
     if (rc != OGC_OK) return rc;
     OGC_REQUIRE(cout >= 1 && w && grad_y && pa && pb && coef && grad_w1, "%s: bad shape or null pointer", name);
@@ -962,10 +1126,18 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_first(int b, int cin, int cout, int hw,
     first.run = ogc_divup(tiles, chunks);
     dim3 grid(ogc_divup(tiles, first.run), b);
     const int cp = ogc_first_cp(c0);
+    // (list form: the same grid — the worst case, every step live, is as many tiles — and the run derived on the device)
 #define OGC_DGAF(KQV, CPV)                                                                                                  \
-    hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, float, false, CPV>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, \
-                       relu, w, grad_y, (const float *)nullptr, pa, pb, coef, (const float2 *)nullptr, (const float2 *)nullptr, 0, \
-                       (float *)nullptr, first)
+    do {                                                                                                                    \
+        if (ls.steps)                                                                                                       \
+            hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, float, false, CPV, true>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, \
+                               K, hw, relu, w, grad_y, (const float *)nullptr, pa, pb, coef, (const float2 *)nullptr,       \
+                               (const float2 *)nullptr, 0, (float *)nullptr, first, ls);                                    \
+        else                                                                                                                \
+            hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, float, false, CPV>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, \
+                               hw, relu, w, grad_y, (const float *)nullptr, pa, pb, coef, (const float2 *)nullptr,          \
+                               (const float2 *)nullptr, 0, (float *)nullptr, first, ls);                                    \
+    } while (0)
     if (Kq <= 8) {
         if (cp == 3) OGC_DGAF(8, 3); else if (cp == 6) OGC_DGAF(8, 6); else OGC_DGAF(8, 8);
     } else {
@@ -973,5 +1145,61 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_first(int b, int cin, int cout, int hw,
     }
 #undef OGC_DGAF
     OGC_CHECK_LAUNCH(name);
+    return OGC_OK;
+}
+} // namespace
+
+extern "C" int ogc_conv1x1_wgrad_moments_first(int b, int cin, int cout, int hw, int relu, int c0, const float *x0, const float *w1,
+                                               const float *pa, const float *pb, const float *grad_y, float *moments,
+                                               ogc_stream_t stream) {
+    return wgrad_moments_first_impl("ogc_conv1x1_wgrad_moments_first", b, cin, cout, hw, relu, c0, x0, w1, pa, pb, grad_y, moments,
+                                    stream);
+}
+
+extern "C" int ogc_conv1x1_dgrad_adjoint_first(int b, int cin, int cout, int hw, int relu, int c0, const float *w,
+                                               const float *grad_y, const float *x0, const float *w1, const float *pa,
+                                               const float *pb, const float *coef, float *grad_w1, ogc_stream_t stream) {
+    return dgrad_adjoint_first_impl("ogc_conv1x1_dgrad_adjoint_first", b, cin, cout, hw, relu, c0, w, grad_y, x0, w1, pa, pb, coef,
+                                    grad_w1, stream);
+}
+
+// The list forms: grad_y needs values at the positions of live steps only (what ogc_conv1x1_dgrad_adjoint_pooled_live writes).
+extern "C" int ogc_conv1x1_wgrad_moments_first_live(int b, int cin, int cout, int hw, int relu, int c0, int nsample, const float *x0,
+                                                    const float *w1, const float *pa, const float *pb, const float *grad_y,
+                                                    const int *live, const int *n_live, int live_cap, float *moments,
+                                                    ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_wgrad_moments_first_live";
+    LiveIn ls;
+    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    if (rc != OGC_OK) return rc;
+    return wgrad_moments_first_impl(name, b, cin, cout, hw, relu, c0, x0, w1, pa, pb, grad_y, moments, stream, ls);
+}
+
+extern "C" int ogc_conv1x1_dgrad_adjoint_first_live(int b, int cin, int cout, int hw, int relu, int c0, int nsample, const float *w,
+                                                    const float *grad_y, const float *x0, const float *w1, const float *pa,
+                                                    const float *pb, const float *coef, const int *live, const int *n_live,
+                                                    int live_cap, float *grad_w1, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_dgrad_adjoint_first_live";
+    LiveIn ls;
+    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    if (rc != OGC_OK) return rc;
+    return dgrad_adjoint_first_impl(name, b, cin, cout, hw, relu, c0, w, grad_y, x0, w1, pa, pb, coef, grad_w1, stream, ls);
+}
+
+// live (b, p * s / 16), n_live (b): the live-step list of a neighbour list idx (b, p, s) (LiveIn above).
+extern "C" int ogc_live_steps(int b, int p, int s, const int *idx, int *live, int *n_live, ogc_stream_t stream) {
+    OGC_REQUIRE(b >= 0 && p >= 1, "ogc_live_steps: bad shape");
+    if (s != 16 && s != 32 && s != 64) {
+        ogc_set_error("ogc_live_steps: nsample=%d must be 16, 32 or 64", s);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    OGC_REQUIRE(idx && live && n_live, "ogc_live_steps: null pointer");
+    if (p > LIVE_MAX_P) {
+        ogc_set_error("ogc_live_steps: p=%d centres per sample, at most %d", p, LIVE_MAX_P);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    if (b == 0) return OGC_OK;
+    hipLaunchKernelGGL(live_steps_kernel, dim3(b), dim3(1024), 0, (hipStream_t)stream, p, s, idx, live, n_live);
+    OGC_CHECK_LAUNCH("ogc_live_steps");
     return OGC_OK;
 }

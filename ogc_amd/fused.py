@@ -956,14 +956,54 @@ def norm_act_conv(y_prev, stats_prev, gn, relu, conv, next_gn=None, pool=0):
 FIRST_PAIR_FUSED = True
 FIRST_PAIR_MAX_C0 = 8
 
+# ---- a first level's backward over the LIVE steps of its neighbour lists only ---------------------------------------------------
+# A neighbour list ends in repeats of its first entry wherever the search found fewer than nsample points inside the radius
+# (utils/pointnet2_util.py:59-79) — at a first level of 8192-point outdoor clouds most of every list.  Every kernel of the chain
+# first pair -> pooled tail is column-wise, so the repeats carry bit-equal values and gradients; only sums over positions see them,
+# and there a weight stands for them.  The geometry plan leaves, per scale, the list of 16-column steps that hold anything else
+# (ogc_live_steps; include/ogc_ops.h has the rule), and the four backward kernels of the chain walk that list: the pooled tail writes
+# the gradient of the pair's output at live positions only and the pair reads it there only.  The forward pass, its statistics and
+# its extremes are untouched.  Taken only when BOTH nodes of the level take it (a first pair followed directly by a pooled tail in
+# moment form), fp32, not in deterministic mode, nsample 32 or 64; False: the dense walks (tools/step_ab.py SKIP_REPEAT_STEPS).
+SKIP_REPEAT_STEPS = True
+
+
+def live_steps(idx):
+    """(live, n_live) of the neighbour lists idx (B, P, S), or None where the list forms would not be taken.  Coordinate-only:
+    part of a level's geometry plan."""
+    nat = _api._native
+    if not (SKIP_REPEAT_STEPS and torch.is_grad_enabled() and idx is not None and idx.is_cuda and idx.dim() == 3
+            and idx.shape[2] in (32, 64) and idx.shape[1] <= 32768 and not deterministic() and getattr(nat, "live_steps_wrapper", None) is not None
+            and nat.get_matmul_precision() == "fp32"):
+        return None
+    return nat.live_steps_wrapper((idx if idx.dtype is torch.int32 else idx.int()).contiguous())
+
+
+class LiveLink:
+    """One forward pass of one scale: the live-step list and what the two nodes of the chain decided (the pair runs first
+    forwards, the tail first backwards; each takes the list only if the other does)."""
+    __slots__ = ("live", "n_live", "pair", "tail")
+
+    def __init__(self, live):
+        self.live, self.n_live = live
+        self.pair = self.tail = False
+
+    def fits(self, B, P, S):
+        return (SKIP_REPEAT_STEPS and S in (32, 64) and tuple(self.live.shape) == (B, P * S // 16)
+                and tuple(self.n_live.shape) == (B,) and not deterministic()
+                and getattr(_api._native, "conv1x1_dgrad_adjoint_first_live_wrapper", None) is not None)
+
 
 class _FirstPairConv(Function):
     """y2 = conv(act(GroupNorm(conv(x0, W1))), W2) for an input x0 (B, c0 <= 8, ...) that needs no gradient.
     Returns (y2, statistics of y2 for the next GroupNorm), as _NormActConv does."""
 
     @staticmethod
-    def forward(ctx, x0, w1, gn_weight, gn_bias, w2, gn_groups, eps, relu, next_groups):
+    def forward(ctx, x0, w1, gn_weight, gn_bias, w2, gn_groups, eps, relu, next_groups, link=None):
         ctx.set_materialize_grads(False)
+        ctx.link = None
+        if link is not None and x0.dim() == 4 and link.fits(x0.shape[0], x0.shape[2], x0.shape[3]):
+            ctx.link, link.pair = link, True
         nat = _api._native
         B, c0 = x0.shape[0], x0.shape[1]
         c1, c2 = w1.shape[0], w2.shape[0]
@@ -990,8 +1030,9 @@ class _FirstPairConv(Function):
     @staticmethod
     def backward(ctx, grad_y, _grad_stats=None):
         if grad_y is None:
-            return (None,) * 9
+            return (None,) * 10
         nat = _api._native
+        link = ctx.link if (ctx.link is not None and ctx.link.tail) else None   # (else grad_y is dense: the dense walk)
         x0, w1, gn_weight, w2, mean, rstd, a, bb = ctx.saved_tensors
         gn_groups, relu, hw = ctx.cfg
         B, c0 = x0.shape[0], x0.shape[1]
@@ -1000,15 +1041,23 @@ class _FirstPairConv(Function):
         grad_y = grad_y.contiguous()
         w1c, w2c = w1.contiguous().view(c1, c0), w2.contiguous().view(c2, c1)
         moments = zeroed_empty((B, 2, c2, c1), torch.float32, dev)
-        nat.conv1x1_wgrad_moments_first_wrapper(B, c1, c2, hw, relu, c0, x0, w1c, a, bb, grad_y, moments)
+        if link is not None:
+            nat.conv1x1_wgrad_moments_first_live_wrapper(B, c1, c2, hw, relu, c0, x0.shape[3], x0, w1c, a, bb, grad_y, link.live,
+                                                         link.n_live, moments)
+        else:
+            nat.conv1x1_wgrad_moments_first_wrapper(B, c1, c2, hw, relu, c0, x0, w1c, a, bb, grad_y, moments)
         grad_w2 = zeroed_empty((c2, c1), torch.float32, dev)
         coef = torch.empty(B, c1, 3, dtype=torch.float32, device=dev)
         ggb = zeroed_empty((2, c1), torch.float32, dev)
         nat.gn_moments_combine_wrapper(B, c1, c2, hw, gn_groups, moments, w2c, a, bb, mean, rstd, gn_weight.contiguous(),
                                        grad_w2, coef, ggb[0], ggb[1])
         grad_w1 = zeroed_empty((c1, c0), torch.float32, dev)
-        nat.conv1x1_dgrad_adjoint_first_wrapper(B, c1, c2, hw, relu, c0, w2c, grad_y, x0, w1c, a, bb, coef, grad_w1)
-        return None, grad_w1.view_as(w1), ggb[0], ggb[1], grad_w2.view_as(w2), None, None, None, None
+        if link is not None:
+            nat.conv1x1_dgrad_adjoint_first_live_wrapper(B, c1, c2, hw, relu, c0, x0.shape[3], w2c, grad_y, x0, w1c, a, bb, coef,
+                                                         link.live, link.n_live, grad_w1)
+        else:
+            nat.conv1x1_dgrad_adjoint_first_wrapper(B, c1, c2, hw, relu, c0, w2c, grad_y, x0, w1c, a, bb, coef, grad_w1)
+        return None, grad_w1.view_as(w1), ggb[0], ggb[1], grad_w2.view_as(w2), None, None, None, None, None
 
 
 def _plain_conv(conv):
@@ -1039,10 +1088,10 @@ def first_pair_available(x, conv, gn, conv2, gn2):
             and max(c1, c2) * hw < 2 ** 31 and x.shape[0] <= 32768)
 
 
-def first_pair_conv(x, conv, gn, relu, conv2, gn2):
-    """(y2, statistics of y2 for gn2) = conv2(act(gn(conv(x)))), see _FirstPairConv."""
+def first_pair_conv(x, conv, gn, relu, conv2, gn2, link=None):
+    """(y2, statistics of y2 for gn2) = conv2(act(gn(conv(x)))), see _FirstPairConv.  link: the scale's LiveLink or None."""
     return _FirstPairConv.apply(x, conv.weight, gn.weight, gn.bias, conv2.weight, gn.num_groups, gn.eps, bool(relu),
-                                gn2.num_groups)
+                                gn2.num_groups, link)
 
 
 # The tail of a set-abstraction MLP — last convolution, its GroupNorm / ReLU, the max over the neighbourhood — as ONE autograd
@@ -1067,11 +1116,17 @@ class _NormActConvPool(Function):
 
     @staticmethod
     def forward(ctx, y_prev, stats_prev, gn_weight, gn_bias, conv_weight, gn_groups, eps, relu, gn2_weight, gn2_bias,
-                groups2, eps2, relu2):
+                groups2, eps2, relu2, link=None):
         nat = _api._native
         y_prev = y_prev.contiguous()
         B, cin, P, S = y_prev.shape
         cout = conv_weight.shape[0]
+        # the live-step list: only behind a first pair that took it (nothing else may read the gradient this node then writes at
+        # live positions only), in moment form, fp32
+        ctx.link = None
+        if (link is not None and link.pair and y_prev.dtype is torch.float32 and link.fits(B, P, S)
+                and cin <= _moment_width(y_prev) and cout <= _pool_moment_cout(y_prev)):
+            ctx.link, link.tail = link, True
         y, stats, extremes, mean, rstd, a, bb = _norm_act_conv_forward(y_prev, stats_prev, gn_weight, gn_bias, conv_weight,
                                                                        gn_groups, eps, relu, groups2, S, gn2_weight)
         dev = y_prev.device
@@ -1117,10 +1172,15 @@ class _NormActConvPool(Function):
             ws = nat.group_norm_ws(B, cin, gn_groups, True, dev)
             nat.group_norm_bwd_wrapper(B, cin, hw, gn_groups, relu, y_prev, gn_weight.contiguous(), gn_bias.contiguous(), mean,
                                        rstd, grad_z, grad_prev, gw, gb, ws)
-            return (grad_prev, None, gw, gb, grad_w.view_as(conv_weight), None, None, None, gw2, gb2, None, None, None)
+            return (grad_prev, None, gw, gb, grad_w.view_as(conv_weight), None, None, None, gw2, gb2, None, None, None, None)
         # the convolution's backward (as _NormActConv.backward's moment-matrix path) on that form
+        link = ctx.link
         moments = zeroed_empty((B, 2, cout, cin), torch.float32, dev)
-        nat.conv1x1_wgrad_moments_pooled_wrapper(B, cin, cout, hw, relu, S, y_prev, a, bb, y, coef2, inj, moments)
+        if link is not None:
+            nat.conv1x1_wgrad_moments_pooled_live_wrapper(B, cin, cout, hw, relu, S, y_prev, a, bb, y, coef2, inj, link.live,
+                                                          link.n_live, moments)
+        else:
+            nat.conv1x1_wgrad_moments_pooled_wrapper(B, cin, cout, hw, relu, S, y_prev, a, bb, y, coef2, inj, moments)
         coef = torch.empty(B, cin, 3, dtype=torch.float32, device=dev)
         ggb = zeroed_empty((2, cin), torch.float32, dev)
         gw, gb = ggb[0], ggb[1]
@@ -1128,8 +1188,12 @@ class _NormActConvPool(Function):
         nat.gn_moments_combine_wrapper(B, cin, cout, hw, gn_groups, moments, w, a, bb, mean, rstd,
                                        gn_weight.contiguous(), grad_w, coef, gw, gb)
         grad_prev = torch.empty_like(y_prev)
-        nat.conv1x1_dgrad_adjoint_pooled_wrapper(B, cin, cout, hw, relu, S, w, y, coef2, inj, y_prev, a, bb, coef, grad_prev)
-        return (grad_prev, None, gw, gb, grad_w.view_as(conv_weight), None, None, None, gw2, gb2, None, None, None)
+        if link is not None:   # (written at live positions only: the pair's list forms read nothing else)
+            nat.conv1x1_dgrad_adjoint_pooled_live_wrapper(B, cin, cout, hw, relu, S, w, y, coef2, inj, y_prev, a, bb, coef,
+                                                          link.live, link.n_live, grad_prev)
+        else:
+            nat.conv1x1_dgrad_adjoint_pooled_wrapper(B, cin, cout, hw, relu, S, w, y, coef2, inj, y_prev, a, bb, coef, grad_prev)
+        return (grad_prev, None, gw, gb, grad_w.view_as(conv_weight), None, None, None, gw2, gb2, None, None, None, None)
 
 
 @_gate
@@ -1160,9 +1224,9 @@ def norm_act_conv_pool_available(y_prev, gn, conv, next_gn):
             and g2 <= 32 and cout % g2 == 0 and (cout // g2) % 4 == 0)
 
 
-def norm_act_conv_pool(y_prev, stats_prev, gn, relu, conv, next_gn, next_relu):
+def norm_act_conv_pool(y_prev, stats_prev, gn, relu, conv, next_gn, next_relu, link=None):
     return _NormActConvPool.apply(y_prev, stats_prev, gn.weight, gn.bias, conv.weight, gn.num_groups, gn.eps, bool(relu),
-                                  next_gn.weight, next_gn.bias, next_gn.num_groups, next_gn.eps, bool(next_relu))
+                                  next_gn.weight, next_gn.bias, next_gn.num_groups, next_gn.eps, bool(next_relu), link)
 
 
 class _SelfAttentionCore(Function):

@@ -831,6 +831,48 @@ def conv1x1_dgrad_adjoint_pooled_wrapper(b, cin, cout, hw, relu, nsample, w, y, 
          _f(coef2, "coef2"), _f(inj, "inj"), ypp, _f(pa, "pa"), _f(pb, "pb"), _f(coef, "coef"), op)
 
 
+def live_steps_wrapper(idx):
+    """(live (B, P * S / 16) int32, n_live (B) int32): the live-step list of the neighbour lists idx (B, P, S) int32
+    (ogc_live_steps; include/ogc_ops.h gives the rule and the packing)."""
+    B, P, S = idx.shape
+    live = torch.empty(B, P * max(S // 16, 1), dtype=torch.int32, device=idx.device)
+    n_live = torch.empty(B, dtype=torch.int32, device=idx.device)
+    _run("ogc_live_steps", idx, B, P, S, _i(idx, "idx"), _i(live, "live"), _i(n_live, "n_live"))
+    return live, n_live
+
+
+def _live_args(live, n_live):
+    return (_opt(live, torch.int32, "live"), _opt(n_live, torch.int32, "n_live"),
+            0 if live is None else live.numel() // max(live.shape[0], 1))
+
+
+def conv1x1_wgrad_moments_pooled_live_wrapper(b, cin, cout, hw, relu, nsample, y_prev, pa, pb, y, coef2, inj, live, n_live,
+                                              moments):
+    _run("ogc_conv1x1_wgrad_moments_pooled_live", y_prev, b, cin, cout, hw, int(relu), nsample, _f(y_prev, "y_prev"),
+         _f(pa, "pa"), _f(pb, "pb"), _f(y, "y"), _f(coef2, "coef2"), _f(inj, "inj"), *_live_args(live, n_live),
+         _f(moments, "moments"))
+
+
+def conv1x1_dgrad_adjoint_pooled_live_wrapper(b, cin, cout, hw, relu, nsample, w, y, coef2, inj, y_prev, pa, pb, coef, live,
+                                              n_live, grad_prev):
+    """grad_prev is written at the positions of live steps only."""
+    _run("ogc_conv1x1_dgrad_adjoint_pooled_live", y, b, cin, cout, hw, int(relu), nsample, _f(w, "w"), _f(y, "y"),
+         _f(coef2, "coef2"), _f(inj, "inj"), _f(y_prev, "y_prev"), _f(pa, "pa"), _f(pb, "pb"), _f(coef, "coef"),
+         *_live_args(live, n_live), _f(grad_prev, "grad_prev"))
+
+
+def conv1x1_wgrad_moments_first_live_wrapper(b, cin, cout, hw, relu, c0, nsample, x0, w1, pa, pb, grad_y, live, n_live, moments):
+    _run("ogc_conv1x1_wgrad_moments_first_live", x0, b, cin, cout, hw, int(relu), c0, nsample, _f(x0, "x0"), _f(w1, "w1"),
+         _f(pa, "pa"), _f(pb, "pb"), _f(grad_y, "grad_y"), *_live_args(live, n_live), _f(moments, "moments"))
+
+
+def conv1x1_dgrad_adjoint_first_live_wrapper(b, cin, cout, hw, relu, c0, nsample, w, grad_y, x0, w1, pa, pb, coef, live, n_live,
+                                             grad_w1):
+    _run("ogc_conv1x1_dgrad_adjoint_first_live", x0, b, cin, cout, hw, int(relu), c0, nsample, _f(w, "w"), _f(grad_y, "grad_y"),
+         _f(x0, "x0"), _f(w1, "w1"), _f(pa, "pa"), _f(pb, "pb"), _f(coef, "coef"), *_live_args(live, n_live),
+         _f(grad_w1, "grad_w1"))
+
+
 def mlp_chain_pool_supported(c0, c1, c2, c3, nsample):
     """Is there a fused inference kernel for the MLP c0 -> c1 -> c2 [-> c3] followed by the max over nsample?"""
     return bool(_lib.load().ogc_mlp_chain_pool_supported(c0, c1, c2, c3, nsample))

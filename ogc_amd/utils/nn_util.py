@@ -166,16 +166,18 @@ class SharedMLP(nn.Sequential):
                                    preact=preact))
 
 
-def _shared_mlp_run(self, x, pool, first=None):
+def _shared_mlp_run(self, x, pool, first=None, live=None):
     """The layers in sequence.  Inside the stack the output of conv -> GroupNorm -> ReLU is only read by the next
     convolution, so on the GPU it is never written: the raw convolution output travels on together with the norm's
     statistics (`pending`) and the norm is applied by the next convolution while loading (fused.norm_act_conv).  The
     last layer's norm / activation (/ max over the neighbourhood, `pool`) is one fused op.
     first: optional callable (conv, gn) -> (raw output, statistics) that evaluates the FIRST layer's convolution (a set-
-    abstraction level fuses it with the grouping, fused.grouped_first_layer); `x` is then unused."""
+    abstraction level fuses it with the grouping, fused.grouped_first_layer); `x` is then unused.
+    live: optional live-step list of the level's neighbour lists (fused.live_steps) for a first pair followed by a pooled tail."""
     from ..fused import (act16_middle_ok, group_norm_act, group_norm_act_maxpool, norm_act_conv, norm_act_conv_available,
                          norm_act_conv_pool, norm_act_conv_pool_available, pointwise_conv)
     layers = list(self.children())
+    link = None   # the live-step list on its way from the first pair to the pooled tail directly behind it
     pending = None  # (raw conv output, its GroupNorm statistics or None, the GroupNorm, relu?, neighbourhood extremes)
 
     def flush(p, last):
@@ -204,7 +206,10 @@ def _shared_mlp_run(self, x, pool, first=None):
             from ..fused import first_pair_available, first_pair_conv
             (conv, gn, relu), (conv2, gn2, relu2) = block(layer), block(layers[1])
             if first_pair_available(x, conv, gn, conv2, gn2):
-                y, stats = first_pair_conv(x, conv, gn, relu, conv2, gn2)
+                if live is not None and pool and len(layers) == 3:
+                    from ..fused import LiveLink
+                    link = LiveLink(live)
+                y, stats = first_pair_conv(x, conv, gn, relu, conv2, gn2, link)
                 pending, skip = (y, stats, gn2, relu2, None), True
                 continue
         if not fusable:
@@ -230,7 +235,8 @@ def _shared_mlp_run(self, x, pool, first=None):
                 # extremes, from which the pooled activation follows without reading its output again
                 if norm_act_conv_pool_available(pending[0], pending[2], conv, gn):
                     # ... and one autograd node for the whole tail: no dense gradient between the pooling and the convolution
-                    return norm_act_conv_pool(pending[0], pending[1], pending[2], pending[3], conv, gn, relu)
+                    return norm_act_conv_pool(pending[0], pending[1], pending[2], pending[3], conv, gn, relu,
+                                              link if li == 2 else None)
                 y, stats, extremes = norm_act_conv(pending[0], pending[1], pending[2], pending[3], conv, gn,
                                                    pool=pending[0].shape[-1])
             else:
@@ -249,10 +255,10 @@ def _shared_mlp_forward(self, x):
     return _shared_mlp_run(self, x, False)
 
 
-def _shared_mlp_forward_maxpool(self, x, first=None):
+def _shared_mlp_forward_maxpool(self, x, first=None, live=None):
     """SharedMLP applied to (B, C, npoint, nsample) followed by the max over nsample
     (reference: utils/pointnet2_util.py:38-42); the last layer's norm/activation/pooling run as one fused op."""
-    return _shared_mlp_run(self, x, True, first)
+    return _shared_mlp_run(self, x, True, first, live)
 
 
 def _shared_mlp_first_layer(self):

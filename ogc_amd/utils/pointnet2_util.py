@@ -36,7 +36,18 @@ class _PointnetSAModuleBase(nn.Module):
         plan = self.plan_sampling(xyz, parent_ties)
         plan["idx"] = self.plan_neighbours(xyz, plan["new_xyz"])
         plan["rev"] = self.plan_reverse(plan["idx"], xyz.shape[1])
+        plan["live"] = self.plan_live(plan["idx"])
         return plan
+
+    def plan_live(self, idx):
+        """The live-step list of every scale whose MLP can run as first pair + pooled tail (three layers on a narrow grouped
+        input: fused.SKIP_REPEAT_STEPS), for the backward kernels of that chain; only where a gradient will be asked for."""
+        from .. import fused as _fused
+
+        def chain(mlp):
+            head = mlp.first_layer() if len(mlp) == 3 else None
+            return head is not None and head[0].weight.shape[1] <= _fused.FIRST_PAIR_MAX_C0
+        return [_fused.live_steps(j) if (j is not None and chain(mlp)) else None for j, mlp in zip(idx, self.mlps)]
 
     def plan_reverse(self, idx, n):
         """Transposed neighbour lists (which (centre, slot) positions point at each source point) of every scale, for the
@@ -90,6 +101,8 @@ class _PointnetSAModuleBase(nn.Module):
             geometry = dict(geometry, idx=self.plan_neighbours(xyz, geometry["new_xyz"]))
         if geometry is not None and "rev" not in geometry:
             geometry = dict(geometry, rev=self.plan_reverse(geometry["idx"], xyz.shape[1]))
+        if geometry is not None and "live" not in geometry:
+            geometry = dict(geometry, live=self.plan_live(geometry["idx"]))
         new_xyz = geometry["new_xyz"] if geometry is not None else None
         new_inds = geometry["new_inds"] if geometry is not None else None
 
@@ -106,8 +119,9 @@ class _PointnetSAModuleBase(nn.Module):
                                                                           act16=len(mlp) >= 2)))
                     continue
                 grouped = grouper(xyz, new_xyz, features, idx=nn_idx)[0]
-            else:
-                grouped = grouper(xyz, new_xyz, features)[0]  # (B, C', npoint, nsample)
+                pooled.append(mlp.forward_maxpool(grouped, live=geometry["live"][i]))
+                continue
+            grouped = grouper(xyz, new_xyz, features)[0]      # (B, C', npoint, nsample)
             pooled.append(mlp.forward_maxpool(grouped))       # shared MLP, then max over nsample (:38-42)
         new_features = torch.cat(pooled, dim=1) if len(pooled) != 1 else pooled[0]   # (one scale: nothing to join, no copy)
         if return_inds:
