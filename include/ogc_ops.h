@@ -53,7 +53,8 @@ enum {
  * The supervised mask loss (ogc_sup_loss_ws_doubles, ogc_sup_match_cost, ogc_sup_mask_loss_fwd / _bwd) likewise: new entry points
  * only, and two tests of 0.2.8 pin the number.  ogc_seg_eval_ignore likewise: a new entry point, ogc_seg_eval unchanged.
  * ogc_soft_carry likewise: a new entry point, no prototype changed.  ogc_scan_crop_camera / _front / _tile and ogc_box_segm /
- * _chunk likewise.  ogc_kittisf_unproject and ogc_png_unfilter likewise. */
+ * _chunk likewise.  ogc_kittisf_unproject and ogc_png_unfilter likewise.  ogc_live_steps_fwd, ogc_conv1x1_gemm_affine_first_live
+ * and ogc_conv1x1_gemm_affine_pool_live likewise. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -747,6 +748,35 @@ int ogc_conv1x1_dgrad_adjoint_first_live(int b, int cin, int cout, int hw, int r
                                          const float *grad_y, const float *x0, const float *w1, const float *pa, const float *pb,
                                          const float *coef, const int *live, const int *n_live, int live_cap, float *grad_w1,
                                          ogc_stream_t stream);
+
+/* The two FORWARD kernels of the same chain over the live steps only (fp32): ogc_conv1x1_gemm_affine_first and
+ * ogc_conv1x1_gemm_affine_pool read their input and write `out` at the positions of live steps ONLY — a skipped position of `out`
+ * keeps whatever it held, and nothing of the chain's backward list forms reads it.
+ *   The forward list.  A wave of these kernels owns a TILE of four list entries and must hold every live entry of each 64-position
+ *       tile of the dense kernels it touches (a GROUP: the entries with the same entry >> 2 — one centre at nsample 64, a pair of
+ *       centres at 32).  ogc_live_steps_fwd writes `live` / `n_live` exactly as ogc_live_steps does and, in the same launch, fwd
+ *       (b, p * T), n_fwd (b): the same entries in the same order, packed greedily so that no group crosses a tile boundary — a
+ *       group that does not fit the slots left in the current tile starts the next one, and the slots it leaves hold the PAD marker
+ *       -1 (every real entry is >= 0).  n_fwd counts entries and the pads in front of the last one; slots behind entry n_fwd - 1 are
+ *       read as pads.  Every tile holds at least one whole group, so p * T entries cover the worst case.  nsample in {32, 64},
+ *       p * nsample a multiple of 64, p <= 32768.
+ *   The statistics are the dense form's: per dense tile and 16-row block the dense kernel adds ONE fp32 partial sum of 256 values,
+ *       (Q0 + Q1) + (Q2 + Q3) with Qs the sum over step s (four lanes of 4 rows x 4 positions each, rows outer, then two exchange
+ *       stages inside the quad of lanes); the list form takes Qs of a live step from the quad that holds it and Qs of a skipped step
+ *       as (d + d) + (d + d), d being what each lane of that step would have summed: the four rows of the last column of the centre's
+ *       last live step, four times each.  The partial sums are therefore bit-equal, and `stats` differs from the dense form's only in
+ *       the order of its fp64 additions, as two runs of the dense form do.  yext / aext (b, M, centres) are the dense form's: maxima
+ *       are exact in any order, and with the smallest index winning a tie every arg-max lies in a live step.
+ *   live, n_live, live_cap of the two *_live entry points: the FORWARD list; otherwise the arguments and preconditions of the entry
+ *       points without the suffix and of the list forms above (K <= 64 for the pooled one). */
+int ogc_live_steps_fwd(int b, int p, int nsample, const int *idx, int *live, int *n_live, int *fwd, int *n_fwd, ogc_stream_t stream);
+int ogc_conv1x1_gemm_affine_first_live(int b, int M, int K, int hw, int relu, int groups, int c0, int nsample, const float *w,
+                                       const float *x0, const float *w1, const float *pa, const float *pb, const int *live,
+                                       const int *n_live, int live_cap, float *out, double *stats, ogc_stream_t stream);
+int ogc_conv1x1_gemm_affine_pool_live(int b, int M, int K, int hw, int relu, int groups, int nsample, const float *w,
+                                      const float *in, const float *pa, const float *pb, const float *next_gamma, const int *live,
+                                      const int *n_live, int live_cap, float *out, double *stats, float *yext, int *aext,
+                                      ogc_stream_t stream);
 
 /* A whole per-neighbourhood MLP and its max-pool in one launch, for INFERENCE
  *   utils/flowstep3d_util.py:57-66 (FlowEmbedding, the correlation layer) and :126-138 (set abstraction):

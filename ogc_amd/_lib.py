@@ -133,6 +133,11 @@ SIGNATURES = {
                                              _vp],
     "ogc_conv1x1_dgrad_adjoint_first_live": [_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _int, _vp, _vp],
+    "ogc_live_steps_fwd": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_conv1x1_gemm_affine_first_live": [_int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int,
+                                           _vp, _vp, _vp],
+    "ogc_conv1x1_gemm_affine_pool_live": [_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                          _vp, _vp, _vp, _vp],
     "ogc_mlp_chain_pool_supported": [_int, _int, _int, _int, _int],
     "ogc_mlp_chain_pool":[_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_corr_layer_pool_supported": [_int, _int, _int, _int, _int],

@@ -42,8 +42,14 @@ namespace {
 // the extremes are then those of the ROUNDED outputs.
 // FIRST (0: off, else the CP of first_conv.h): `in` is the output of a first convolution that was never stored — the tile is
 // rebuilt from first.x0 and first.w1 (K = c1 <= 64 rows of W1 in LDS), everything after the load is the same.
+// LIST (fp32, STATS and PRO, FIRST or POOL): a wave's tile is FOUR ENTRIES of the sample's forward live-step list (live_steps.h)
+// instead of 64 consecutive positions — lane j holds positions 4 (j & 3) .. + 3 of entry 4 tile + (j >> 2), as in the list forms of
+// gn_fused_bwd.hip.  Input is read and `out` written at live positions only; a pad slot loads zeros, stores nothing and enters no
+// sum or extreme.  A column's MFMA sequence is the dense form's, so the values are; the statistics rebuild every dense tile's fp32
+// partial sums (ogc_live_stats_epilogue) and the extremes join a centre's entries (ogc_live_pool_epilogue): conv1x1_epilogue.h.
+// The grid is the dense form's (the worst case: every step live); workgroups beyond the list leave at once.
 template <bool TRANSPOSE_A, int KQ, bool STATS, bool PRO, bool BF, bool POOL = false, typename IT = float, typename OT = float,
-          int FIRST = 0>
+          int FIRST = 0, bool LIST = false>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M, int K, int hw, int groups,
                                                                           const float *__restrict__ w, // (Cout, Cin)
                                                                           const IT *__restrict__ in,
@@ -51,17 +57,33 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M,
                                                                           double *__restrict__ stats,
                                                                           const float *__restrict__ pa,
                                                                           const float *__restrict__ pb, int pro_relu,
-                                                                          PoolOut pool = PoolOut(), FirstIn first = FirstIn()) {
+                                                                          PoolOut pool = PoolOut(), FirstIn first = FirstIn(),
+                                                                          LiveIn ls = LiveIn()) {
     extern __shared__ __attribute__((aligned(16))) float a_lds[]; // [64][ogc_a_ld(Kq)]: the current 64-row tile of A (conv_stage.h)
     __shared__ __attribute__((aligned(16))) float s_w1[FIRST ? FC_MAX_ROWS * FC_MAX_C0 : 4];
     __shared__ double s_stats[STATS ? 64 : 1];                    // [groups][2]
     __shared__ __attribute__((aligned(16))) float s_sign[POOL ? 64 : 4]; // POOL: -1 for the tile's rows whose next scale is negative
+    __shared__ __attribute__((aligned(16))) float s_live[LIST ? WG_WAVES * LIVE_WAVE_FLOATS : 4]; // LIST: a strip per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 15, kk = lane >> 4;
     const int b = blockIdx.y;
     const int p0 = (blockIdx.x * WG_WAVES + wave) * 64;
     const int Kq = (K + 3) >> 2, a_ld = ogc_a_ld(Kq);
-    const bool live = p0 < hw; // hw is a multiple of 64 for every wave that is live
+    bool live = p0 < hw; // hw is a multiple of 64 for every wave that is live
+    int pos = p0 + 4 * j; // the lane's first position
+    bool lane_live = live; // LIST: ... and the lane's slot holds an entry
+    LiveTile lt = LiveTile();
+    if constexpr (LIST) {
+        static_assert(STATS && PRO && !BF && !TRANSPOSE_A && sizeof(IT) == 4 && sizeof(OT) == 4 && (POOL || FIRST > 0),
+                      "list form: fp32, first-layer or pooled, with statistics");
+        const int n_lv = min(ls.n[b], ls.cap);
+        if ((int)blockIdx.x * 4 * WG_WAVES >= n_lv) return; // (the whole workgroup, ahead of every barrier)
+        const int tile = blockIdx.x * WG_WAVES + wave;
+        live = 4 * tile < n_lv;
+        lt = ogc_live_tile(ls.steps + (size_t)b * ls.cap, n_lv, tile, hw, POOL && pool.s == 32 ? 5 : 6, j);
+        pos = lt.pos;
+        lane_live = live && lt.ok;
+    }
     const IT *inb = in + (size_t)b * K * hw;
     OT *outb = out + (size_t)b * M * hw;
     if (STATS && threadIdx.x < 2 * groups) s_stats[threadIdx.x] = 0.0;
@@ -71,8 +93,8 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M,
         static_assert(KQ * 4 <= FC_MAX_ROWS && sizeof(IT) == 4 && !TRANSPOSE_A, "first-layer form: fp32, at most 64 rows of W1");
         ogc_first_stage_w1<WG_WAVES * OGC_WAVE>(s_w1, first.w1, K, first.c0);
         float4 x0v[FIRST];
-        ogc_first_load_raw<FIRST>(x0v, first.x0 + (size_t)b * first.c0 * hw + (live ? p0 + 4 * j : 0), first.c0, hw);
-        ogc_first_mask<FIRST>(x0v, first.c0, live);
+        ogc_first_load_raw<FIRST>(x0v, first.x0 + (size_t)b * first.c0 * hw + (lane_live ? pos : 0), first.c0, hw);
+        ogc_first_mask<FIRST>(x0v, first.c0, lane_live);
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < KQ; ++q) { // rows beyond K meet zero weights in s_w1: exact zeros, as the loads of the stored form
@@ -84,7 +106,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M,
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
         const int row = q * 4 + kk;
-        xin[q] = (live && q < Kq && row < K) ? ogc_ld4(inb + (size_t)row * hw + p0 + 4 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+        xin[q] = (lane_live && q < Kq && row < K) ? ogc_ld4(inb + (size_t)row * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     }
     if (PRO) { // a second pass, so that all loads above are in flight before the first one is waited for; in chunks
@@ -243,12 +265,17 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M,
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int m = m0 + a * 16 + kk * 4 + r; // C/D layout: row (l >> 4) * 4 + r, column l & 15
-                    if (m < M) {
+                    if (m < M && (!LIST || lane_live)) {
                         const float4 o = make_float4(acc[a][0][r], acc[a][1][r], acc[a][2][r], acc[a][3][r]);
-                        ogc_st4(outb + (size_t)m * hw + p0 + 4 * j, o);
+                        ogc_st4(outb + (size_t)m * hw + pos, o);
                     }
                 }
-            if constexpr (POOL) {
+            if constexpr (POOL && LIST) {
+                const int centres = hw / pool.s;
+                const size_t o0 = ((size_t)b * M + m0 + kk * 4) * centres;
+                ogc_live_pool_epilogue(acc, nblk, lt, s_live + wave * LIVE_WAVE_FLOATS, s_sign, j, kk, m0, M, centres, pool.s,
+                                       pool.yext + o0, pool.aext + o0);
+            } else if constexpr (POOL) {
                 const int centres = hw / pool.s;
                 const int centre = (p0 + 4 * j) / pool.s;    // of this lane's four positions
                 // outputs of row m0 + kk * 4 of this lane's centre; row a * 16 + r is (a * 16 + r) * centres further on
@@ -257,25 +284,24 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void conv1x1_gemm_kernel(int M,
                 else if (pool.s == 32) ogc_pool_extremes_epilogue<8>(acc, nblk, s_sign, j, kk, m0, M, centres, 32, pool.yext + o0, pool.aext + o0);
                 else ogc_pool_extremes_epilogue<4>(acc, nblk, s_sign, j, kk, m0, M, centres, 16, pool.yext + o0, pool.aext + o0);
             }
-            if (STATS) {
+            if constexpr (STATS && LIST) {
+                ogc_live_stats_epilogue(acc, nblk, lt, s_live + wave * LIVE_WAVE_FLOATS, j, kk, [&](int a, float sm, float sq) {
+                    const int m = m0 + a * 16 + kk * 4;
+                    if (m < M) {
+                        atomicAdd(&s_stats[2 * (m / cpg)], (double)sm);
+                        atomicAdd(&s_stats[2 * (m / cpg) + 1], (double)sq);
+                    }
+                });
+            } else if (STATS) {
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     if (a < nblk) {
                         // the lane's 4 rows (m .. m+3) x 4 positions; rows >= M are exact zeros
-                        float sm = 0.f, sq = 0.f;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) {
-                                const float v = acc[a][c][r];
-                                sm += v;
-                                sq += v * v;
-                            }
+                        float sm, sq;
+                        ogc_stats_lane_sum(acc[a][0], acc[a][1], acc[a][2], acc[a][3], sm, sq);
                         // sum over the 16 lanes of the DPP row (same rows, the other 60 positions)
-                        sm += ogc_dpp_f32<0xB1>(sm); sq += ogc_dpp_f32<0xB1>(sq);
-                        sm += ogc_dpp_f32<0x4E>(sm); sq += ogc_dpp_f32<0x4E>(sq);
-                        sm += ogc_dpp_f32<0x141>(sm); sq += ogc_dpp_f32<0x141>(sq);
-                        sm += ogc_dpp_f32<0x140>(sm); sq += ogc_dpp_f32<0x140>(sq);
+                        ogc_stats_quad_sum(sm, sq);
+                        ogc_stats_row_sum(sm, sq);
                         const int m = m0 + a * 16 + kk * 4;
                         if (j == 0 && m < M) {
                             const int g = m / cpg;
@@ -925,10 +951,11 @@ extern "C" int ogc_first_conv_stats(int b, int c1, int c0, int hw, int groups, c
 
 // ogc_conv1x1_gemm_affine with output statistics on in = conv(x0, w1), which is rebuilt while the tile is loaded: the tile kernel
 // (the persistent form of conv1x1_h.hip gives the same bits where it would have run: its test pins that).
-extern "C" int ogc_conv1x1_gemm_affine_first(int b, int M, int K, int hw, int relu, int groups, int c0, const float *w,
-                                             const float *x0, const float *w1, const float *pa, const float *pb, float *out,
-                                             double *stats, ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_gemm_affine_first";
+namespace {
+template <bool LIST>
+int gemm_affine_first_impl(const char *name, int b, int M, int K, int hw, int relu, int groups, int c0, const float *w,
+                           const float *x0, const float *w1, const float *pa, const float *pb, float *out, double *stats,
+                           ogc_stream_t stream, LiveIn ls = LiveIn()) {
     int rc = first_check(name, b, K, c0, hw, x0, w1);
     if (rc != OGC_OK) return rc;
     OGC_REQUIRE(M >= 1 && w && pa && pb && out && stats, "%s: bad shape or null pointer", name);
@@ -950,15 +977,74 @@ extern "C" int ogc_conv1x1_gemm_affine_first(int b, int M, int K, int hw, int re
     FirstIn first;
     first.x0 = x0; first.w1 = w1; first.c0 = c0;
 #define OGC_GEMM_FIRST(KQV, CPV)                                                                                           \
-    hipLaunchKernelGGL((conv1x1_gemm_kernel<false, KQV, true, true, false, false, float, float, CPV>), grid,               \
+    hipLaunchKernelGGL((conv1x1_gemm_kernel<false, KQV, true, true, false, false, float, float, CPV, LIST>), grid,         \
                        dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, groups, w, (const float *)nullptr, out, stats, pa, pb, relu, \
-                       PoolOut(), first)
+                       PoolOut(), first, ls)
     if (Kq <= 8) {
         if (cp == 3) OGC_GEMM_FIRST(8, 3); else if (cp == 6) OGC_GEMM_FIRST(8, 6); else OGC_GEMM_FIRST(8, 8);
     } else {
         if (cp == 3) OGC_GEMM_FIRST(16, 3); else if (cp == 6) OGC_GEMM_FIRST(16, 6); else OGC_GEMM_FIRST(16, 8);
     }
 #undef OGC_GEMM_FIRST
+    OGC_CHECK_LAUNCH(name);
+    return OGC_OK;
+}
+} // namespace
+
+extern "C" int ogc_conv1x1_gemm_affine_first(int b, int M, int K, int hw, int relu, int groups, int c0, const float *w,
+                                             const float *x0, const float *w1, const float *pa, const float *pb, float *out,
+                                             double *stats, ogc_stream_t stream) {
+    return gemm_affine_first_impl<false>("ogc_conv1x1_gemm_affine_first", b, M, K, hw, relu, groups, c0, w, x0, w1, pa, pb, out,
+                                         stats, stream);
+}
+
+// ---- the list forms of the two forward kernels of a first level's chain (LIST at conv1x1_gemm_kernel; live_steps.h) --------------
+// live, n_live: the FORWARD list of ogc_live_steps_fwd.  x0 / `in` are read and `out` is written at the positions of live steps
+// only; stats hold the dense form's fp32 partial sums (they differ from its result in the order of fp64 additions, as two runs of
+// it do); yext / aext are the dense form's.
+extern "C" int ogc_conv1x1_gemm_affine_first_live(int b, int M, int K, int hw, int relu, int groups, int c0, int nsample,
+                                                  const float *w, const float *x0, const float *w1, const float *pa,
+                                                  const float *pb, const int *live, const int *n_live, int live_cap, float *out,
+                                                  double *stats, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_gemm_affine_first_live";
+    LiveIn ls;
+    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    if (rc != OGC_OK) return rc;
+    return gemm_affine_first_impl<true>(name, b, M, K, hw, relu, groups, c0, w, x0, w1, pa, pb, out, stats, stream, ls);
+}
+
+extern "C" int ogc_conv1x1_gemm_affine_pool_live(int b, int M, int K, int hw, int relu, int groups, int nsample, const float *w,
+                                                 const float *in, const float *pa, const float *pb, const float *next_gamma,
+                                                 const int *live, const int *n_live, int live_cap, float *out, double *stats,
+                                                 float *yext, int *aext, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_gemm_affine_pool_live";
+    LiveIn ls;
+    int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    if (rc != OGC_OK) return rc;
+    rc = gemm_check(name, b, M, K, hw, w, in, out);
+    if (rc != OGC_OK) return rc;
+    OGC_REQUIRE(pa && pb && next_gamma && stats && yext && aext, "%s: null pointer", name);
+    if (groups < 1 || groups > 32 || M % groups != 0 || (M / groups) % 4 != 0 || K > 64 || g_matmul_bf16) {
+        ogc_set_error("%s: needs fp32 operands, 1 <= groups <= 32, (M / groups) %% 4 == 0 and K <= 64 (M=%d, groups=%d, K=%d)", name,
+                      M, groups, K);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    if (b == 0) return OGC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (ogc_zero_async(stats, sizeof(double) * 2 * GN_SLOTS * (size_t)b * groups, s) != hipSuccess) {
+        ogc_set_error("%s: memset failed", name);
+        return OGC_ERR_LAUNCH;
+    }
+    PoolOut pool;
+    pool.yext = yext; pool.aext = aext; pool.sign = next_gamma; pool.s = nsample;
+    const int Kq = (K + 3) / 4;
+    const size_t lds = (size_t)64 * ogc_a_ld(Kq) * sizeof(float);
+    dim3 grid(ogc_divup(hw, 64 * WG_WAVES), b); // (the worst case, every step live, is as many tiles of four entries)
+#define OGC_GEMM_POOL_LIVE(KQV)                                                                                            \
+    hipLaunchKernelGGL((conv1x1_gemm_kernel<false, KQV, true, true, false, true, float, float, 0, true>), grid,            \
+                       dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, groups, w, in, out, stats, pa, pb, relu, pool, FirstIn(), ls)
+    if (Kq <= 8) OGC_GEMM_POOL_LIVE(8); else OGC_GEMM_POOL_LIVE(16);
+#undef OGC_GEMM_POOL_LIVE
     OGC_CHECK_LAUNCH(name);
     return OGC_OK;
 }

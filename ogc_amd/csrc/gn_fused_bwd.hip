@@ -24,33 +24,27 @@
 #include "conv1x1_shared.h" // v4f, WG_WAVES, ogc_pooled_grad, the operand precision switch ogc_g_matmul_bf16 (conv1x1.hip)
 #include "act_io.h"
 #include "first_conv.h"
+#include "live_steps.h"
 
 namespace {
 
 // ---- live steps: the 16-position steps of a level's neighbourhoods that hold more than repeats of column 0 ------------------------
-// A neighbour list idx (B, P, S) ends in repeats of its first entry wherever the search found fewer than S points inside the
-// radius (utils/pointnet2_util.py:59-79).  Every kernel of a level's chain is column-wise, so those columns carry bit-equal
-// values and gradients; only sums over positions see them, and there a weight stands for them.  Per centre
-//     fill = 1 + max{ j : idx[j] != idx[0] }  (1: none),   T = S / 16,   s* = min(fill / 16, T - 1):
-// steps 0 .. s* are LIVE, steps s* + 1 .. T - 1 are skipped; when s* < T - 1 the last column of step s* is a repeat (16 (s* + 1) >
-// fill) and stands for itself and the 16 (T - 1 - s*) skipped columns.  The list of a sample: its live steps ascending, entry =
-// position / 16, with the skipped-step count T - 1 - s* in the bits from LIVE_SHIFT up ON THE ENTRY OF STEP s* (zero on the
-// others: the weight 1 + 16 * (entry >> LIVE_SHIFT) belongs to that step's last position alone); n[b] entries of `cap` are used.
-constexpr int LIVE_SHIFT = 28;
-constexpr int LIVE_MASK = (1 << LIVE_SHIFT) - 1;
-struct LiveIn {
-    const int *steps = nullptr; // (B, cap)
-    const int *n = nullptr;     // (B)
-    int cap = 0;
-};
+// (the rule, the packing of both lists, LiveIn and live_check: live_steps.h, shared with the forward list forms of conv1x1.hip)
 
 // One workgroup per sample.  Count: a wavefront reads 64 consecutive entries (64 / S whole rows) per load and finds each row's last
 // column that differs from column 0 with a ballot; the centre's live-step count goes to LDS.  Then a run of consecutive centres
 // per thread: sum, scan (as rev_scan_kernel of neighbour_loss.hip), write.
+// FWD: the forward list as well (live_steps.h; p * s is a multiple of 64).  The greedy pack is a walk over the groups with one
+// state, the slots u = 0 .. 3 used in the current tile; a run of groups maps u to the slots it consumes from there, pads included
+// (the state after it is (u + that) & 3), and such maps compose — a thread forms the map of its run of consecutive groups, the
+// same scan composes them, and the thread writes its run from the offset the runs in front of it consume from state 0.
 constexpr int LIVE_MAX_P = 32768; // centres per sample (one byte of LDS each)
+template <bool FWD>
 __global__ __launch_bounds__(1024) void live_steps_kernel(int p, int s, const int *__restrict__ idx, int *__restrict__ steps,
-                                                          int *__restrict__ n_live) {
+                                                          int *__restrict__ n_live, int *__restrict__ fwd = nullptr,
+                                                          int *__restrict__ n_fwd = nullptr) {
     __shared__ int part[1024];
+    __shared__ int fmap[FWD ? 4 * 1024 : 4]; // FWD: [u][thread] slots consumed from state u
     __shared__ unsigned char cnt[LIVE_MAX_P];
     const int t = threadIdx.x, b = blockIdx.x, T = s >> 4;
     const int lane = t & 63, wave = t >> 6;
@@ -86,6 +80,58 @@ __global__ __launch_bounds__(1024) void live_steps_kernel(int p, int s, const in
         for (int st = 0; st <= sl; ++st) out[at++] = (c * T + st) | (st == sl ? (T - 1 - sl) << LIVE_SHIFT : 0);
     }
     if (t == 1023) n_live[b] = part[1023];
+    if constexpr (FWD) {
+        const int cpg = 4 / T;                 // centres per group: 1 (s = 64) or 2 (s = 32)
+        const int groups = p / cpg;            // (p * T is a multiple of 4)
+        const int gper = (groups + 1023) / 1024;
+        const int g0 = min(t * gper, groups), g1 = min(g0 + gper, groups);
+        auto group_size = [&](int g) { return cpg == 1 ? (int)cnt[g] : (int)cnt[2 * g] + (int)cnt[2 * g + 1]; };
+        int len[4] = {0, 0, 0, 0};
+        for (int g = g0; g < g1; ++g) {
+            const int sz = group_size(g);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int used = (u + len[u]) & 3;
+                len[u] += (used + sz > 4 ? 4 - used : 0) + sz;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) fmap[u * 1024 + t] = len[u];
+        __syncthreads();
+        for (int off = 1; off < 1024; off <<= 1) { // inclusive scan: the runs t - off + 1 .. t, composed left to right
+            int left[4] = {0, 0, 0, 0};
+            if (t >= off) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) left[u] = fmap[u * 1024 + t - off];
+            }
+            __syncthreads();
+            if (t >= off) {
+                int mine[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) mine[u] = fmap[((u + left[u]) & 3) * 1024 + t];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) left[u] += mine[u];
+            }
+            __syncthreads();
+            if (t >= off) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) fmap[u * 1024 + t] = left[u];
+            }
+            __syncthreads();
+        }
+        int *fo = fwd + (size_t)b * p * T;
+        int fat = t > 0 ? fmap[t - 1] : 0; // from state 0
+        for (int g = g0; g < g1; ++g) {
+            const int used = fat & 3;
+            if (used + group_size(g) > 4)
+                for (int u = used; u < 4; ++u) fo[fat++] = LIVE_PAD;
+            for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
+                const int sl = cnt[c] - 1;
+                for (int st = 0; st <= sl; ++st) fo[fat++] = (c * T + st) | (st == sl ? (T - 1 - sl) << LIVE_SHIFT : 0);
+            }
+        }
+        if (t == 1023) n_fwd[b] = fmap[1023];
+    }
 }
 
 // ---- moment matrices ------------------------------------------------------------------------------------------------
@@ -811,20 +857,6 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
 namespace {
 int nsample_shift(int nsample) { return nsample == 16 ? 4 : nsample == 32 ? 5 : nsample == 64 ? 6 : -1; }
 
-// the list forms' own preconditions (checked ahead of every launch and memset): a list with room for the worst case, every step
-// live — n_live stays on the device, so a list shorter than that could be shorter than n_live — and S = 32 or 64
-int live_check(const char *name, const int *live, const int *n_live, int live_cap, int hw, int nsample, LiveIn &ls) {
-    OGC_REQUIRE(live && n_live, "%s: null live-step list", name);
-    if (nsample != 32 && nsample != 64) {
-        ogc_set_error("%s: the list form needs nsample 32 or 64 (nsample=%d)", name, nsample);
-        return OGC_ERR_UNSUPPORTED;
-    }
-    OGC_REQUIRE(hw >= 16 && hw % nsample == 0 && (hw >> 4) <= LIVE_MASK && live_cap >= (hw >> 4),
-                "%s: the live-step list holds %d entries per sample, hw=%d needs room for %d", name, live_cap, hw, hw >> 4);
-    ls.steps = live; ls.n = n_live; ls.cap = live_cap;
-    return OGC_OK;
-}
-
 template <typename AT>
 int wgrad_moments_impl(const char *name, int b, int cin, int cout, int hw, int relu, const AT *y_prev, const float *pa,
                        const float *pb, const AT *grad_y, const float *coef2, const float *inj, int s_shift,
@@ -1199,7 +1231,27 @@ extern "C" int ogc_live_steps(int b, int p, int s, const int *idx, int *live, in
         return OGC_ERR_UNSUPPORTED;
     }
     if (b == 0) return OGC_OK;
-    hipLaunchKernelGGL(live_steps_kernel, dim3(b), dim3(1024), 0, (hipStream_t)stream, p, s, idx, live, n_live);
+    hipLaunchKernelGGL(live_steps_kernel<false>, dim3(b), dim3(1024), 0, (hipStream_t)stream, p, s, idx, live, n_live);
     OGC_CHECK_LAUNCH("ogc_live_steps");
+    return OGC_OK;
+}
+
+// ogc_live_steps, and in the same launch the forward list fwd (b, p * s / 16), n_fwd (b) (live_steps.h): the same entries packed so
+// that no 64-position group crosses a tile of four entries.  s in {32, 64}, p * s a multiple of 64.
+extern "C" int ogc_live_steps_fwd(int b, int p, int s, const int *idx, int *live, int *n_live, int *fwd, int *n_fwd,
+                                  ogc_stream_t stream) {
+    OGC_REQUIRE(b >= 0 && p >= 1, "ogc_live_steps_fwd: bad shape");
+    if ((s != 32 && s != 64) || (p * (long long)s) % 64 != 0) {
+        ogc_set_error("ogc_live_steps_fwd: needs nsample 32 or 64 and p * nsample %% 64 == 0 (p=%d, nsample=%d)", p, s);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    OGC_REQUIRE(idx && live && n_live && fwd && n_fwd, "ogc_live_steps_fwd: null pointer");
+    if (p > LIVE_MAX_P) {
+        ogc_set_error("ogc_live_steps_fwd: p=%d centres per sample, at most %d", p, LIVE_MAX_P);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    if (b == 0) return OGC_OK;
+    hipLaunchKernelGGL(live_steps_kernel<true>, dim3(b), dim3(1024), 0, (hipStream_t)stream, p, s, idx, live, n_live, fwd, n_fwd);
+    OGC_CHECK_LAUNCH("ogc_live_steps_fwd");
     return OGC_OK;
 }

@@ -799,9 +799,10 @@ def _pool_moment_cout(t):
 
 
 def _norm_act_conv_forward(y_prev, stats_prev, gn_weight, gn_bias, conv_weight, gn_groups, eps, relu, next_groups, pool,
-                           next_gamma):
+                           next_gamma, live_link=None):
     """y = conv(act(GroupNorm(y_prev))) with the norm applied on the way in (shared by _NormActConv and _NormActConvPool).
-    -> (y, statistics of y or None, neighbourhood extremes or None, mean, rstd, a, bb of the norm of y_prev)."""
+    -> (y, statistics of y or None, neighbourhood extremes or None, mean, rstd, a, bb of the norm of y_prev).
+    live_link: a LiveLink whose forward list the pooled convolution walks (y_prev read, y written at live positions only)."""
     nat = _api._native
     B, cin = y_prev.shape[0], y_prev.shape[1]
     cout = conv_weight.shape[0]
@@ -830,11 +831,20 @@ def _norm_act_conv_forward(y_prev, stats_prev, gn_weight, gn_bias, conv_weight, 
             centres = hw // pool
             yext = torch.empty(B, cout, centres, dtype=torch.float32, device=dev)
             aext = torch.empty(B, cout, centres, dtype=torch.int32, device=dev)
-            nat.conv1x1_gemm_affine_pool_wrapper(B, cout, cin, hw, relu, next_groups, pool, w, y_prev, a, bb,
-                                                 next_gamma.contiguous(), y, stats, yext, aext)
+            if live_link is not None:
+                nat.conv1x1_gemm_affine_pool_live_wrapper(B, cout, cin, hw, relu, next_groups, pool, w, y_prev, a, bb,
+                                                          next_gamma.contiguous(), live_link.fwd, live_link.n_fwd, y, stats,
+                                                          yext, aext)
+            else:
+                nat.conv1x1_gemm_affine_pool_wrapper(B, cout, cin, hw, relu, next_groups, pool, w, y_prev, a, bb,
+                                                     next_gamma.contiguous(), y, stats, yext, aext)
             extremes = (yext, aext)
+        elif live_link is not None:
+            raise _live_chain_broken("the pooled convolution does not take the extremes path")
         else:
             nat.conv1x1_gemm_affine_wrapper(B, cout, cin, hw, relu, next_groups, w, y_prev, a, bb, y, stats)
+    elif live_link is not None:
+        raise _live_chain_broken("the pooled convolution does not form statistics")
     else:
         nat.conv1x1_gemm_affine_wrapper(B, cout, cin, hw, relu, 0, w, y_prev, a, bb, y, None)
     return y, stats, extremes, mean, rstd, a, bb
@@ -962,36 +972,75 @@ FIRST_PAIR_MAX_C0 = 8
 # first pair -> pooled tail is column-wise, so the repeats carry bit-equal values and gradients; only sums over positions see them,
 # and there a weight stands for them.  The geometry plan leaves, per scale, the list of 16-column steps that hold anything else
 # (ogc_live_steps; include/ogc_ops.h has the rule), and the four backward kernels of the chain walk that list: the pooled tail writes
-# the gradient of the pair's output at live positions only and the pair reads it there only.  The forward pass, its statistics and
-# its extremes are untouched.  Taken only when BOTH nodes of the level take it (a first pair followed directly by a pooled tail in
+# the gradient of the pair's output at live positions only and the pair reads it there only.  (The forward pass: LIVE_FORWARD
+# below.)  Taken only when BOTH nodes of the level take it (a first pair followed directly by a pooled tail in
 # moment form), fp32, not in deterministic mode, nsample 32 or 64; False: the dense walks (tools/step_ab.py SKIP_REPEAT_STEPS).
 SKIP_REPEAT_STEPS = True
 
+# ---- ... and its forward over the live steps --------------------------------------------------------------------------------------
+# The two forward kernels of the same chain (the pair's second layer, the pooled tail) walk a list as well: they read their input
+# and write y2 / y3 at live positions only — nothing of the backward list forms reads anything else — and reproduce the dense
+# kernels' statistics (the same fp32 partial sums: include/ogc_ops.h) and extremes, so the level's output is bit-identical.  The
+# geometry plan leaves a second, tile-aligned list for them (ogc_live_steps_fwd).  A pair that writes y2 sparsely OBLIGES the tail
+# to the list forms, forwards and backwards, so the chain is decided as a whole before the pair runs (LiveLink.plan_forward):
+# everything SKIP_REPEAT_STEPS asks for, a tail that takes the one-node extremes path in moment form with its pooled sums from
+# the extremes, and a gradient being asked for.  The tail's list form on a dense y2 is valid, the reverse is not:
+# LIVE_FORWARD_PAIR = False keeps the pair dense.  False: the dense forward (tools/step_ab.py LIVE_FORWARD).
+LIVE_FORWARD = True
+LIVE_FORWARD_PAIR = True
+
 
 def live_steps(idx):
-    """(live, n_live) of the neighbour lists idx (B, P, S), or None where the list forms would not be taken.  Coordinate-only:
-    part of a level's geometry plan."""
+    """(live, n_live[, fwd, n_fwd]) of the neighbour lists idx (B, P, S), or None where the list forms would not be taken; the
+    forward list only where the forward list forms may be.  Coordinate-only: part of a level's geometry plan."""
     nat = _api._native
     if not (SKIP_REPEAT_STEPS and torch.is_grad_enabled() and idx is not None and idx.is_cuda and idx.dim() == 3
             and idx.shape[2] in (32, 64) and idx.shape[1] <= 32768 and not deterministic() and getattr(nat, "live_steps_wrapper", None) is not None
             and nat.get_matmul_precision() == "fp32"):
         return None
-    return nat.live_steps_wrapper((idx if idx.dtype is torch.int32 else idx.int()).contiguous())
+    idx = (idx if idx.dtype is torch.int32 else idx.int()).contiguous()
+    if (LIVE_FORWARD and (idx.shape[1] * idx.shape[2]) % 64 == 0
+            and getattr(nat, "conv1x1_gemm_affine_pool_live_wrapper", None) is not None):
+        return nat.live_steps_fwd_wrapper(idx)
+    return nat.live_steps_wrapper(idx)
 
 
 class LiveLink:
-    """One forward pass of one scale: the live-step list and what the two nodes of the chain decided (the pair runs first
-    forwards, the tail first backwards; each takes the list only if the other does)."""
-    __slots__ = ("live", "n_live", "pair", "tail")
+    """One forward pass of one scale: the live-step lists and what the two nodes of the chain decided (the pair runs first
+    forwards, the tail first backwards; each takes the backward list only if the other does).  forward / forward_pair: the tail /
+    the pair as well run their FORWARD list forms — decided for the whole chain by plan_forward before the pair runs."""
+    __slots__ = ("live", "n_live", "fwd", "n_fwd", "pair", "tail", "forward", "forward_pair")
 
     def __init__(self, live):
-        self.live, self.n_live = live
-        self.pair = self.tail = False
+        self.live, self.n_live = live[0], live[1]
+        self.fwd, self.n_fwd = (live[2], live[3]) if len(live) == 4 else (None, None)
+        self.pair = self.tail = self.forward = self.forward_pair = False
+
+    def plan_forward(self, x0, conv2, gn2, conv3, gn3):
+        """Decide the forward list forms for the chain first pair (x0 -> conv2's output y2) -> pooled tail (gn2, conv3, gn3)."""
+        nat = _api._native
+        B, P, S = x0.shape[0], x0.shape[2], x0.shape[3]
+        c2, c3 = conv2.weight.shape[0], conv3.weight.shape[0]
+        y2 = x0.new_empty(1).expand(B, c2, P, S)   # (shape and type of the pair's output: nothing is allocated)
+        self.forward = bool(
+            LIVE_FORWARD and self.fwd is not None and torch.is_grad_enabled() and x0.dtype is torch.float32
+            and nat.get_matmul_precision() == "fp32" and self.fits(B, P, S) and tuple(self.fwd.shape) == tuple(self.live.shape)
+            and tuple(self.n_fwd.shape) == (B,) and POOL_SUMS_FROM_EXTREMES and (P * S) % 64 == 0
+            and getattr(nat, "conv1x1_gemm_affine_pool_live_wrapper", None) is not None
+            and c2 <= min(_moment_width(y2), 64) and c3 <= _pool_moment_cout(y2) and gn3.affine
+            and c3 % gn3.num_groups == 0 and (c3 // gn3.num_groups) % 4 == 0
+            and norm_act_conv_pool_available.__wrapped__(y2, gn2, conv3, gn3))
+        self.forward_pair = self.forward and LIVE_FORWARD_PAIR
 
     def fits(self, B, P, S):
         return (SKIP_REPEAT_STEPS and S in (32, 64) and tuple(self.live.shape) == (B, P * S // 16)
                 and tuple(self.n_live.shape) == (B,) and not deterministic()
                 and getattr(_api._native, "conv1x1_dgrad_adjoint_first_live_wrapper", None) is not None)
+
+
+def _live_chain_broken(what):
+    return RuntimeError("first level over live steps: %s — the chain was planned for the list forms (LiveLink.plan_forward) and "
+                        "what the forward pass wrote is valid at live positions only" % what)
 
 
 class _FirstPairConv(Function):
@@ -1004,6 +1053,9 @@ class _FirstPairConv(Function):
         ctx.link = None
         if link is not None and x0.dim() == 4 and link.fits(x0.shape[0], x0.shape[2], x0.shape[3]):
             ctx.link, link.pair = link, True
+        sparse = link is not None and link.forward_pair   # y2 at live positions only
+        if sparse and ctx.link is None:
+            raise _live_chain_broken("the first pair cannot take the list")
         nat = _api._native
         B, c0 = x0.shape[0], x0.shape[1]
         c1, c2 = w1.shape[0], w2.shape[0]
@@ -1021,7 +1073,11 @@ class _FirstPairConv(Function):
                                       slots, None, mean, rstd, a, bb)
         y2 = torch.empty((B, c2) + tuple(x0.shape[2:]), dtype=torch.float32, device=dev)
         stats2 = zeroed_empty(slots * B * next_groups * 2, torch.float64, dev)
-        nat.conv1x1_gemm_affine_first_wrapper(B, c2, c1, hw, relu, next_groups, c0, w2c, x0, w1c, a, bb, y2, stats2)
+        if sparse:
+            nat.conv1x1_gemm_affine_first_live_wrapper(B, c2, c1, hw, relu, next_groups, c0, x0.shape[3], w2c, x0, w1c, a, bb,
+                                                       link.fwd, link.n_fwd, y2, stats2)
+        else:
+            nat.conv1x1_gemm_affine_first_wrapper(B, c2, c1, hw, relu, next_groups, c0, w2c, x0, w1c, a, bb, y2, stats2)
         ctx.save_for_backward(x0, w1, gn_weight, w2, mean, rstd, a, bb)
         ctx.cfg = (gn_groups, relu, hw)
         ctx.mark_non_differentiable(stats2)
@@ -1033,6 +1089,8 @@ class _FirstPairConv(Function):
             return (None,) * 10
         nat = _api._native
         link = ctx.link if (ctx.link is not None and ctx.link.tail) else None   # (else grad_y is dense: the dense walk)
+        if link is None and ctx.link is not None and ctx.link.forward:
+            raise _live_chain_broken("the pooled tail did not take the list")
         x0, w1, gn_weight, w2, mean, rstd, a, bb = ctx.saved_tensors
         gn_groups, relu, hw = ctx.cfg
         B, c0 = x0.shape[0], x0.shape[1]
@@ -1127,8 +1185,12 @@ class _NormActConvPool(Function):
         if (link is not None and link.pair and y_prev.dtype is torch.float32 and link.fits(B, P, S)
                 and cin <= _moment_width(y_prev) and cout <= _pool_moment_cout(y_prev)):
             ctx.link, link.tail = link, True
+        sparse = link is not None and link.forward   # y_prev may hold live positions only, y will
+        if sparse and ctx.link is None:
+            raise _live_chain_broken("the pooled tail cannot take the list")
         y, stats, extremes, mean, rstd, a, bb = _norm_act_conv_forward(y_prev, stats_prev, gn_weight, gn_bias, conv_weight,
-                                                                       gn_groups, eps, relu, groups2, S, gn2_weight)
+                                                                       gn_groups, eps, relu, groups2, S, gn2_weight,
+                                                                       link if sparse else None)
         dev = y_prev.device
         out = torch.empty(B, cout, P, dtype=torch.float32, device=dev)
         arg = torch.empty(B, cout, P, dtype=torch.int32, device=dev)
@@ -1159,6 +1221,8 @@ class _NormActConvPool(Function):
                                                   rstd2, out, arg, grad_out.contiguous(), coef2, inj, gw2, gb2, ws,
                                                   yext if POOL_SUMS_FROM_EXTREMES else None)
         w = conv_weight.contiguous().view(cout, cin)
+        # (a chain whose forward ran over live steps never reaches the dense walks below: its ctx.link is set, which implies the
+        # moment form's widths)
         if cin > _moment_width(y_prev) or cout > _pool_moment_cout(y_prev):
             # wide tails (SA2 64 -> 128, SA3 128 -> 256 at C4): weight and input gradient rebuild g_y from (y, coef2, inj) while
             # they load y (round 4: ogc_conv1x1_wgrad_affine_pooled, ogc_conv1x1_dgrad_pooled) — the pass that wrote the dense g_y

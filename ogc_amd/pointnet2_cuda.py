@@ -873,6 +873,34 @@ def conv1x1_dgrad_adjoint_first_live_wrapper(b, cin, cout, hw, relu, c0, nsample
          _f(grad_w1, "grad_w1"))
 
 
+def live_steps_fwd_wrapper(idx):
+    """(live, n_live) as live_steps_wrapper, and (fwd, n_fwd): the same entries packed for the forward list forms — no group
+    of one 64-position tile crosses a tile of four entries, empty slots hold -1 (ogc_live_steps_fwd)."""
+    B, P, S = idx.shape
+    live = torch.empty(B, P * max(S // 16, 1), dtype=torch.int32, device=idx.device)
+    fwd = torch.empty_like(live)
+    n_live = torch.empty(B, dtype=torch.int32, device=idx.device)
+    n_fwd = torch.empty_like(n_live)
+    _run("ogc_live_steps_fwd", idx, B, P, S, _i(idx, "idx"), _i(live, "live"), _i(n_live, "n_live"), _i(fwd, "fwd"),
+         _i(n_fwd, "n_fwd"))
+    return live, n_live, fwd, n_fwd
+
+
+def conv1x1_gemm_affine_first_live_wrapper(b, M, K, hw, relu, groups, c0, nsample, w, x0, w1, pa, pb, fwd, n_fwd, out, stats):
+    """conv1x1_gemm_affine_first_wrapper over the forward live-step list: out is written at the positions of live steps only."""
+    _run("ogc_conv1x1_gemm_affine_first_live", x0, b, M, K, hw, int(relu), groups, c0, nsample, _f(w, "w"), _f(x0, "x0"),
+         _f(w1, "w1"), _f(pa, "pa"), _f(pb, "pb"), *_live_args(fwd, n_fwd), _f(out, "out"), _check(stats, torch.float64, "stats"))
+
+
+def conv1x1_gemm_affine_pool_live_wrapper(b, M, K, hw, relu, groups, nsample, w, x, pa, pb, next_gamma, fwd, n_fwd, out, stats,
+                                          yext, aext):
+    """conv1x1_gemm_affine_pool_wrapper (fp32) over the forward live-step list: x is read and out written at the positions of
+    live steps only; stats, yext and aext are the dense form's."""
+    _run("ogc_conv1x1_gemm_affine_pool_live", x, b, M, K, hw, int(relu), groups, nsample, _f(w, "w"), _f(x, "x"), _f(pa, "pa"),
+         _f(pb, "pb"), _f(next_gamma, "next_gamma"), *_live_args(fwd, n_fwd), _f(out, "out"),
+         _check(stats, torch.float64, "stats"), _f(yext, "yext"), _i(aext, "aext"))
+
+
 def mlp_chain_pool_supported(c0, c1, c2, c3, nsample):
     """Is there a fused inference kernel for the MLP c0 -> c1 -> c2 [-> c3] followed by the max over nsample?"""
     return bool(_lib.load().ogc_mlp_chain_pool_supported(c0, c1, c2, c3, nsample))

@@ -209,6 +209,11 @@ def _shared_mlp_run(self, x, pool, first=None, live=None):
                 if live is not None and pool and len(layers) == 3:
                     from ..fused import LiveLink
                     link = LiveLink(live)
+                    if x.dim() == 4 and isinstance(layers[2], _ConvNd) and layers[2]._gn_fuse:
+                        # the forward list forms are decided for the whole chain here: a pair that writes its output at live
+                        # positions only needs a tail that reads nothing else
+                        conv3, gn3, _ = block(layers[2])
+                        link.plan_forward(x, conv2, gn2, conv3, gn3)
                 y, stats = first_pair_conv(x, conv, gn, relu, conv2, gn2, link)
                 pending, skip = (y, stats, gn2, relu2, None), True
                 continue
@@ -237,11 +242,18 @@ def _shared_mlp_run(self, x, pool, first=None, live=None):
                     # ... and one autograd node for the whole tail: no dense gradient between the pooling and the convolution
                     return norm_act_conv_pool(pending[0], pending[1], pending[2], pending[3], conv, gn, relu,
                                               link if li == 2 else None)
+            if link is not None and link.forward_pair:   # (plan_forward asked the same questions: not reached)
+                raise RuntimeError("first level over live steps: the tail does not run as one pooled node, and the pair's output "
+                                   "is valid at live positions only")
+            if pool and li == len(layers) - 1 and pending[0].dim() == 4 and pending[0].shape[-1] in (16, 32, 64):
                 y, stats, extremes = norm_act_conv(pending[0], pending[1], pending[2], pending[3], conv, gn,
                                                    pool=pending[0].shape[-1])
             else:
                 y, stats = norm_act_conv(pending[0], pending[1], pending[2], pending[3], conv, gn)
         else:
+            if link is not None and link.forward_pair:
+                raise RuntimeError("first level over live steps: the tail cannot fold the norm into its convolution, and the "
+                                   "pair's output is valid at live positions only")
             if pending is not None:
                 x, pending = flush(pending, False), None
             y, stats = first(conv, gn) if (first is not None and li == 0) else pointwise_conv(x, conv, gn)
