@@ -54,7 +54,7 @@ enum {
  * only, and two tests of 0.2.8 pin the number.  ogc_seg_eval_ignore likewise: a new entry point, ogc_seg_eval unchanged.
  * ogc_soft_carry likewise: a new entry point, no prototype changed.  ogc_scan_crop_camera / _front / _tile and ogc_box_segm /
  * _chunk likewise.  ogc_kittisf_unproject and ogc_png_unfilter likewise.  ogc_live_steps_fwd, ogc_conv1x1_gemm_affine_first_live
- * and ogc_conv1x1_gemm_affine_pool_live likewise. */
+ * and ogc_conv1x1_gemm_affine_pool_live likewise.  ogc_moving_stats / _label_cap likewise. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -623,6 +623,32 @@ int ogc_kittisf_unproject(int height, int width, const unsigned short *disp1, co
  * per complete pixel.  A null pointer, a negative size, bpp not in {1, 2, 3, 6}, row_bytes % bpp != 0, a filter byte above 4:
  * OGC_ERR_INVALID_ARG with a message. */
 int ogc_png_unfilter(const unsigned char *in, unsigned char *out, int height, int row_bytes, int bpp);
+
+/* Data preparation, Waymo: the three integers per frame pair that the selection of moving samples takes, for a ragged batch of B
+ * samples in ONE launch.  Replaces, per pair, data_prepare/waymo/select_mov.py:74-96 and the reader's filter_segm
+ * (datasets/dataset_waymo.py:110-128) on the pair's first frame.
+ * The raw arrays of the first frames, concatenated along points: pc, flow (total, 3) f32; segm, semantic_segm (total,) i32; offsets
+ * (B + 1,) i32, sample b owns the points offsets[b] .. offsets[b + 1] - 1; motion (B, 12) f64, the row-major 3 x 3 rotation r, then
+ * the translation t; ignore_class_ids (n_ignore,) i32.  All device memory.  stats (B, 4) i32 out = {n_distinct, n_fg, n_mov, status}:
+ *   n_distinct  the number of distinct values of the FILTERED labels: a point's label becomes 0 when its semantic class is one of
+ *               ignore_class_ids or when its object has fewer than ignore_npoint_thresh points in this sample.
+ *   n_fg        the points with y >= (float)ground_y, compared in fp32.
+ *   n_mov       those of them with, in fp64 from the fp32 inputs, one rounding per operation, never contracted,
+ *                 d_i = ((((r_i0 x + r_i1 y) + r_i2 z) + t_i) - p_i) - flow_i,   sqrt((d_0^2 + d_1^2) + d_2^2) > moving_thresh
+ *               (strict; the square root correctly rounded; a NaN is not moving).
+ *   status      0, or 1: a label outside [0, OGC_MOVING_STATS_LABEL_CAP), or 2: offsets[b] < 0, offsets[b + 1] < offsets[b] or
+ *               offsets[b + 1] > total.  With a status the other three fields are 0, nothing outside the arrays is read, and the
+ *               other samples are unaffected.  The host only holds the pointer to offsets, so this is where they are checked.
+ * One workgroup per sample, integer LDS atomics and integer reductions only: the result does not depend on the order of the
+ * points or on the launch geometry.  An empty sample gives {0, 0, 0, 0}.  B == 0: OGC_OK, no launch.  A negative B, total,
+ * n_ignore or ignore_npoint_thresh, a ground_y that is not finite, a moving_thresh that is not finite or negative, a null pointer
+ * (the four point arrays may be null when total == 0, ignore_class_ids when n_ignore == 0): OGC_ERR_INVALID_ARG, nothing
+ * launched. */
+#define OGC_MOVING_STATS_LABEL_CAP 4096
+int ogc_moving_stats(int B, int total, const int *offsets, const float *pc, const float *flow, const int *segm,
+                     const int *semantic_segm, const double *motion, const int *ignore_class_ids, int n_ignore,
+                     int ignore_npoint_thresh, double ground_y, double moving_thresh, int *stats, ogc_stream_t stream);
+int ogc_moving_stats_label_cap(void); /* OGC_MOVING_STATS_LABEL_CAP of the library */
 
 /* Attention core of the MaskFormer head's nn.MultiheadAttention layers
  *   utils/transformer_util.py:5-62 (cross-attention slots <- points, self-attention among the slots; 8 heads,

@@ -90,6 +90,8 @@ SIGNATURES = {
     "ogc_kittisf_unproject": [_int, _int, _vp, _vp, _vp, _vp, _flt, _flt, _flt, _flt, _flt, _flt, _flt, _flt, _vp, _int,
                               _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_png_unfilter": [_vp, _vp, _int, _int, _int],   # host code, no stream: the integers last
+    "ogc_moving_stats": [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _dbl, _dbl, _vp, _vp],
+    "ogc_moving_stats_label_cap": [],
     "ogc_group_concat": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_fwd": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_bwd": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],

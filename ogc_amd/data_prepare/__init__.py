@@ -9,6 +9,10 @@ the readers of ogc_amd/datasets.py load.
   png16                  read_png / write_png for 8- and 16-bit grey and RGB PNGs (zlib + ogc_png_unfilter)
   process_kittisf        python -m ogc_amd.data_prepare.process_kittisf <data_root>          (scan_ops.kittisf_unproject)
   downsample_kittisf     python -m ogc_amd.data_prepare.downsample_kittisf <data_root> --save_root S [--predflow_path NAME]
+  downsample_waymo       python -m ogc_amd.data_prepare.downsample_waymo --data_root R --save_root S --split_file F
+  filter_empty           python -m ogc_amd.data_prepare.filter_empty --data_root R --split_file F --out <split>_sup.json   (no device)
+  select_mov             python -m ogc_amd.data_prepare.select_mov --data_root S --pose_root R --split_file F --sup_frames J --out_dir D
+                         (scan_ops.moving_stats / moving_counts over csrc/moving_stats.hip)
 
 A frame is one upload, crop -> FPS -> labels on the device, one download.  There is no CPU path.
 """

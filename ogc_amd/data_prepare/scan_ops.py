@@ -1,5 +1,6 @@
-"""The device operators of data preparation (csrc/scan_prepare.hip; csrc/kittisf_prepare.hip).  Inputs are
-CUDA tensors, results stay on the device; the only host read is the number of kept points of a crop.  There is no CPU path."""
+"""The device operators of data preparation (csrc/scan_prepare.hip; csrc/kittisf_prepare.hip, DESIGN §4k;
+csrc/moving_stats.hip).  Inputs are CUDA tensors, results stay on the device; the only host reads are the number of
+kept points of a crop and moving_counts' copy of its integers.  There is no CPU path."""
 import numpy as np
 import torch
 
@@ -146,3 +147,68 @@ def kittisf_unproject(disp1, disp2, flow, inst, P_rect, select_semantics=KITTISF
                                       depth_thresh, sel, len(select), pc1, pc2, segm, keep_idx, count)
     m = int(count.item())
     return pc1[:m], pc2[:m], segm[:m], keep_idx[:m]
+
+
+MOVING_STATS_LABEL_CAP = _native.MOVING_STATS_LABEL_CAP
+
+
+def moving_stats(pc, flow, segm, semantic_segm, offsets, motion, ignore_class_ids=(), ignore_npoint_thresh=0, ground_y=0.3,
+                 moving_thresh=0.2):
+    """What the selection of moving Waymo samples needs of a ragged batch of B frame pairs (select_mov.py:74-96 with the reader's
+    filter_segm, dataset_waymo.py:110-128), in one launch: the first frames' raw arrays concatenated along points — pc, flow
+    (total, 3) fp32, segm, semantic_segm (total,) int32 —, offsets (B + 1,) int32 delimiting the samples and motion (B, 12) fp64 (the
+    row-major rotation, then the translation of the relative sensor motion), CUDA tensors; ignore_class_ids a sequence of ints
+    -> stats (B, 4) int32 on the device: the number of distinct filtered labels, the points with y >= ground_y, those of them whose
+    flow differs from the rigid flow by more than moving_thresh, and a status (include/ogc_ops.h: ogc_moving_stats)."""
+    tensors = ((pc, "pc", torch.float32), (flow, "flow", torch.float32), (segm, "segm", torch.int32),
+               (semantic_segm, "semantic_segm", torch.int32), (offsets, "offsets", torch.int32), (motion, "motion", torch.float64))
+    for t, name, dtype in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype != dtype:
+            raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    for t, name, _ in tensors:
+        if t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (HIP device); ogc_amd has no CPU path" % name)
+    if pc.dim() != 2 or pc.shape[1] != 3:
+        raise ValueError("pc must be (total, 3), got %s" % (tuple(pc.shape),))
+    total = pc.shape[0]
+    if tuple(flow.shape) != (total, 3):
+        raise ValueError("flow must be (%d, 3), got %s" % (total, tuple(flow.shape)))
+    for t, name in ((segm, "segm"), (semantic_segm, "semantic_segm")):
+        if tuple(t.shape) != (total,):
+            raise ValueError("%s must be (%d,), got %s" % (name, total, tuple(t.shape)))
+    if offsets.dim() != 1 or offsets.shape[0] < 1:
+        raise ValueError("offsets must be (B + 1,), got %s" % (tuple(offsets.shape),))
+    batch = offsets.shape[0] - 1
+    if tuple(motion.shape) != (batch, 12):
+        raise ValueError("motion must be (%d, 12), got %s" % (batch, tuple(motion.shape)))
+    for t, name, _ in tensors:
+        if not t.is_contiguous():
+            raise RuntimeError("%s must be contiguous" % name)
+    if total > 0x7fffffff:
+        raise ValueError("%d points are beyond 32-bit offsets" % total)
+    ignore = [int(c) for c in ignore_class_ids]
+    if int(ignore_npoint_thresh) != ignore_npoint_thresh or ignore_npoint_thresh < 0:
+        raise ValueError("ignore_npoint_thresh must be an integer >= 0, got %r" % (ignore_npoint_thresh,))
+    if not (np.isfinite(ground_y) and np.isfinite(moving_thresh) and moving_thresh >= 0):
+        raise ValueError("ground_y must be finite and moving_thresh finite and >= 0, got %r, %r" % (ground_y, moving_thresh))
+    ign = torch.tensor(ignore, dtype=torch.int32, device=pc.device)
+    stats = torch.empty(batch, 4, dtype=torch.int32, device=pc.device)
+    _native.moving_stats_wrapper(batch, total, offsets, pc, flow, segm, semantic_segm, motion, ign, len(ignore), int(ignore_npoint_thresh),
+                                 ground_y, moving_thresh, stats)
+    return stats
+
+
+MOVING_STATUS = {1: "a label outside [0, %d)" % MOVING_STATS_LABEL_CAP, 2: "offsets that descend or leave the arrays"}
+
+
+def moving_counts(*args, **kwargs):
+    """moving_stats and the single device -> host copy: numpy (B, 3) int32 = {n_distinct, n_fg, n_mov} per sample.  A sample with
+    a status set is a ValueError that names it."""
+    stats = moving_stats(*args, **kwargs).cpu().numpy()
+    bad = np.nonzero(stats[:, 3])[0]
+    if bad.size:
+        raise ValueError("moving_stats: " + "; ".join("sample %d has %s" % (b, MOVING_STATUS.get(int(stats[b, 3]), "status %d" % stats[b, 3]))
+                                                      for b in bad))
+    return stats[:, :3]

@@ -447,6 +447,19 @@ def kittisf_unproject_wrapper(height, width, disp1, disp2, flow, inst, fb, f, p0
          _i(segm, "segm"), _i(keep_idx, "keep_idx"), _i(count, "count"))
 
 
+MOVING_STATS_LABEL_CAP = 4096   # OGC_MOVING_STATS_LABEL_CAP: labels of ogc_moving_stats lie in [0, this)
+
+
+def moving_stats_wrapper(b, total, offsets, pc, flow, segm, semantic_segm, motion, ignore_class_ids, n_ignore, ignore_npoint_thresh,
+                         ground_y, moving_thresh, stats):
+    """The three integers of the moving-sample selection for a ragged batch in one launch (ogc_moving_stats): offsets (b + 1,) i32,
+    pc, flow (total, 3) f32, segm, semantic_segm (total,) i32, motion (b, 12) f64, ignore_class_ids (n_ignore,) i32
+    -> stats (b, 4) i32 = {n_distinct, n_fg, n_mov, status}."""
+    _run("ogc_moving_stats", stats, b, total, _i(offsets, "offsets"), _f(pc, "pc"), _f(flow, "flow"), _i(segm, "segm"),
+         _i(semantic_segm, "semantic_segm"), _check(motion, torch.float64, "motion"), _i(ignore_class_ids, "ignore_class_ids"),
+         int(n_ignore), int(ignore_npoint_thresh), float(ground_y), float(moving_thresh), _i(stats, "stats"))
+
+
 def png_unfilter(stream_bytes, height, row_bytes, bpp):
     """The row filters of an inflated PNG stream undone on the host (ogc_png_unfilter; nothing is launched): bytes of
     height * (1 + row_bytes) -> numpy uint8 (height, row_bytes)."""

@@ -256,6 +256,61 @@ def write_waymo_singleframe_roots(root, n_train, n_val, n_frames, n_points, seed
     return out
 
 
+def write_waymo_moving_root(root, n_sequences, n_frames, n_points, n_sample_point, seed=9400, split="train", n_boxes=4, n_moving=3, ground_frac=0.2,
+                            small_object=12, short_frame=("seq_0000", 2)):
+    """A full-resolution Waymo root for the preparation chain filter_empty -> downsample_waymo -> select_mov, in the layout of
+    write_waymo_root with the poses and float64 flows process_waymo writes.  Sequences of make_waymo_sequence with `n_boxes` boxes
+    and `ground_frac` of the points on the ground (few, so that furthest point sampling, which spreads over the 60 m of ground,
+    still leaves the compact boxes some tens of points each);
+    in the sequences of EVEN number the boxes 1 .. n_moving drive through the static world, box k by velocity[k] per frame, 0.5 to
+    0.9 m in the ground plane: their points of frame t are displaced by t * velocity (seen from the sensor), and the stored
+    backward flow is the rigid flow of the displaced point minus the velocity seen from frame t - 1 — where the point was one
+    frame earlier.  The sequences of odd number stay static: their flows are the rigid flows of write_waymo_root.
+    In every frame `small_object` points of the last box become an object of their own (id n_boxes + 1, class 1), and frame
+    `short_frame` = (sequence, t) is cut to n_sample_point - n_sample_point // 8 points, fewer than the sample count.  Every other
+    frame has at least n_sample_point points (n_points - 5 % must reach it).
+    Returns {"mapping": the split file, "names", "moving": names of the moving sequences, "short_frame", "velocity": {name: (n_boxes + 2, 3)}}."""
+    import os
+
+    import numpy as np
+    assert n_points - n_points // 20 >= n_sample_point and 0 < n_moving <= n_boxes
+    names, moving, velocities = [], [], {}
+    for k in range(n_sequences):
+        name = "seq_%04d" % k
+        frames = make_waymo_sequence(n_frames, n_points, seed=seed + k, ground_frac=ground_frac, n_boxes=n_boxes)
+        rs = np.random.RandomState(seed + 1000 + k)
+        velocity = np.zeros((n_boxes + 2, 3))
+        if k % 2 == 0:
+            angle, speed = rs.rand(n_moving) * 2.0 * np.pi, 0.5 + 0.4 * rs.rand(n_moving)
+            velocity[1:n_moving + 1] = np.stack([speed * np.cos(angle), np.zeros(n_moving), speed * np.sin(angle)], 1)
+            moving.append(name)
+        velocities[name] = velocity
+        d = os.path.join(root, "data", name)
+        os.makedirs(d, exist_ok=True)
+        for t, frame in enumerate(frames):
+            pc, segm, semantic = frame["pc"].copy(), frame["segm"].copy(), frame["semantic_segm"].copy()
+            if (name, t) == tuple(short_frame):
+                cut = n_sample_point - n_sample_point // 8
+                pc, segm, semantic = pc[:cut], segm[:cut], semantic[:cut]
+            rot_t = frame["pose"][:3, :3]
+            pc = (pc.astype(np.float64) + t * (velocity[segm] @ rot_t)).astype(np.float32)      # R^T v, row-wise
+            fragment = np.nonzero(segm == n_boxes)[0][:small_object]
+            stored_segm = segm.copy()
+            stored_segm[fragment], semantic[fragment] = n_boxes + 1, 1
+            for what, value in (("pc", pc), ("segm", stored_segm), ("semantic_segm", semantic), ("pose", frame["pose"])):
+                np.save(os.path.join(d, "%s_%04d.npy" % (what, t)), value)
+            if t >= 1:
+                p1, p2 = frame["pose"], frames[t - 1]["pose"]
+                rot, transl = p2[:3, :3].T @ p1[:3, :3], p2[:3, :3].T @ (p1[:3, 3] - p2[:3, 3])
+                p = pc.astype(np.float64)
+                np.save(os.path.join(d, "flow_%04d_%04d.npy" % (t, t - 1)), p @ rot.T + transl - p - velocity[segm] @ p2[:3, :3])
+        names.append(name)
+    mapping = os.path.join(root, split + ".txt")
+    with open(mapping, "w") as f:
+        f.write("\n".join(names) + "\n")
+    return {"mapping": mapping, "names": names, "moving": moving, "short_frame": tuple(short_frame), "velocity": velocities}
+
+
 LABELLED_LAYOUTS = ("kittisf", "kittidet", "semantickitti")
 SYNTHETIC_SEQUENCES = (0, 8, 12)   # synthetic frames cycle through these; test_seg evaluates sequences 0..10
 
