@@ -54,7 +54,8 @@ enum {
  * only, and two tests of 0.2.8 pin the number.  ogc_seg_eval_ignore likewise: a new entry point, ogc_seg_eval unchanged.
  * ogc_soft_carry likewise: a new entry point, no prototype changed.  ogc_scan_crop_camera / _front / _tile and ogc_box_segm /
  * _chunk likewise.  ogc_kittisf_unproject and ogc_png_unfilter likewise.  ogc_live_steps_fwd, ogc_conv1x1_gemm_affine_first_live
- * and ogc_conv1x1_gemm_affine_pool_live likewise.  ogc_moving_stats / _label_cap likewise. */
+ * and ogc_conv1x1_gemm_affine_pool_live likewise.  ogc_moving_stats / _label_cap likewise.  ogc_surface_candidates, ogc_surface_thin /
+ * _ws_bytes and ogc_nearest_label likewise. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -649,6 +650,52 @@ int ogc_moving_stats(int B, int total, const int *offsets, const float *pc, cons
                      const int *semantic_segm, const double *motion, const int *ignore_class_ids, int n_ignore,
                      int ignore_npoint_thresh, double ground_y, double moving_thresh, int *stats, ogc_stream_t stream);
 int ogc_moving_stats_label_cap(void); /* OGC_MOVING_STATS_LABEL_CAP of the library */
+
+/* Data preparation, OGC-DR: an even sampling of mesh surfaces and the label transfer of the single-view set, what
+ * data_prepare/ogcdr/sample_pointcloud.py does with trimesh.sample.sample_surface_even and data_prepare/ogcdrsv/collect_segm.py with
+ * scipy's cdist.  All buffers device memory; every check that needs their contents is made on the device and reported in a status
+ * buffer the caller reads when it reads the result.  C == 0 (B == 0): OGC_OK, nothing launched.
+ *
+ * ogc_surface_candidates: C area-weighted random points on the triangles of M meshes, fp64.  vertices (V, 3) f64 and faces (F, 3) i32
+ * are the meshes concatenated, the faces indexing the concatenated vertices; cum_area (F) f64 is, per mesh, the running sum of its
+ * face areas 0.5 * |cross|, restarting at each mesh; face_offsets, cand_offsets (M + 1) i32 delimit faces and candidates per mesh.
+ * Candidate j of mesh m draws u0, u1, u2 in [0, 1) from Philox4x32-10 with key (seed & 0xffffffff, seed >> 32): counter (j, m, 0, 0)
+ * gives u0 from words 0, 1 and u1 from words 2, 3, counter (j, m, 1, 0) gives u2 from words 0, 1; u = ((hi >> 5) * 2^26 + (lo >> 6)) *
+ * 2^-53 with hi the first word.  So a candidate depends on (seed, m, j) and its mesh alone.  pick = u0 * total area; the face is the
+ * first whose running sum exceeds pick (searchsorted, side "right"), clamped to the first face whose running sum reaches the total:
+ * a face that adds no area is never chosen (trimesh's side "left" can choose a leading degenerate face at pick == 0).  If u1 + u2 > 1,
+ * (u1, u2) = (1 - u1, 1 - u2); p = (o + u1 * e1) + u2 * e2 per coordinate with o = v[f0], e1 = v[f1] - o, e2 = v[f2] - o, one rounding
+ * per operation.  points (C, 3) f64, face_idx (C) i32 (a row of faces) out.  status (1) i32 out: 0, or 1 a face index outside [0, V),
+ * 2 offsets that do not start at 0, descend or do not end at F / C, 3 a mesh with candidates whose total area is not a positive
+ * finite number; with a status set points and face_idx are not written.  Negative sizes, 3 F beyond 32 bits, C > 0 without a mesh, a
+ * null pointer: OGC_ERR_INVALID_ARG, nothing launched. */
+int ogc_surface_candidates(int C, int M, int V, int F, const double *vertices, const int *faces, const double *cum_area,
+                           const int *face_offsets, const int *cand_offsets, long long seed, double *points, int *face_idx, int *status,
+                           ogc_stream_t stream);
+/* ogc_surface_thin: first-come greedy thinning, exact.  points (C, 3) f64, cand_offsets (M + 1) i32, radius (M) f64; keep (C) i32 out.
+ * The definition is sequential: walking a mesh's candidates in index order, candidate i is kept (1) iff no kept candidate j < i of the
+ * same mesh has ((dx*dx) + (dy*dy)) + (dz*dz) <= r_m * r_m in fp64, one rounding per operation, the bound inclusive; otherwise it is
+ * removed (0).  Candidates of different meshes never interact.  This is the rule trimesh.sample.sample_surface_even documents as
+ * rejection sampling; this definition, not trimesh's code, is the contract.
+ * It is computed in rounds, one launch each (csrc/surface_thin.hip), over a uniform grid built inside the call.  A call with
+ * rounds_done == 0 builds the grid in ws and queues `rounds` rounds; status (3) i32 then holds {code, candidates still undecided,
+ * rounds that decided something}.  While status[1] != 0 the caller calls again with the same buffers and rounds_done = the rounds
+ * queued so far, which queues `rounds` more; keep is final once status[1] == 0.  A round with nothing left to decide returns at once.
+ * code: 0, or 1 a coordinate that is not finite, 2 a radius that is negative or not finite, 3 cand_offsets that do not start at 0,
+ * descend or do not end at C; with a code set keep is not written and status[1] is 0.
+ * ws: ws_bytes >= ogc_surface_thin_ws_bytes(C, M) bytes, 256-byte aligned.  C > 2^26: OGC_ERR_UNSUPPORTED.  Negative sizes, rounds
+ * outside [0, 65536], C > 0 with M == 0, a null pointer, a small or misaligned workspace: OGC_ERR_INVALID_ARG.  Nothing launched. */
+long long ogc_surface_thin_ws_bytes(int C, int M); /* -1 for a C outside [0, 2^26] */
+int ogc_surface_thin(int C, int M, const double *points, const int *cand_offsets, const double *radius, int rounds, int rounds_done,
+                     int *keep, int *status, void *ws, long long ws_bytes, ogc_stream_t stream);
+/* ogc_nearest_label: per query the nearest source point of its sample and that point's label, `labels[cdist(query, source).argmin(1)]`.
+ * query (B, Nq, 3), source (B, Ns, 3) f32, labels (B, Ns) i32; out_label, out_idx (B, Nq) i32.  The distance is
+ * sqrt(((dx*dx) + (dy*dy)) + (dz*dz)) in fp64 from the fp32 inputs, one rounding per operation, the root correctly rounded, and the
+ * ROOT is compared: two squares can round to one root, and the lowest source index among the minima wins, as in numpy's argmin.  A
+ * NaN distance never wins.  B == 0 or Nq == 0: OGC_OK, nothing launched.  Ns < 1 otherwise, B > 65535, B * Nq or B * Ns beyond
+ * 32-bit indexing of the coordinates, a null pointer: OGC_ERR_INVALID_ARG, nothing launched. */
+int ogc_nearest_label(int B, int Nq, int Ns, const float *query, const float *source, const int *labels, int *out_label, int *out_idx,
+                      ogc_stream_t stream);
 
 /* Attention core of the MaskFormer head's nn.MultiheadAttention layers
  *   utils/transformer_util.py:5-62 (cross-attention slots <- points, self-attention among the slots; 8 heads,

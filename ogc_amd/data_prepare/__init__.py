@@ -13,6 +13,23 @@ the readers of ogc_amd/datasets.py load.
   filter_empty           python -m ogc_amd.data_prepare.filter_empty --data_root R --split_file F --out <split>_sup.json   (no device)
   select_mov             python -m ogc_amd.data_prepare.select_mov --data_root S --pose_root R --split_file F --sup_frames J --out_dir D
                          (scan_ops.moving_stats / moving_counts over csrc/moving_stats.hip)
+  mesh_ops               surface_candidates / surface_thin / nearest_label and sample_surface_even — the operators over
+                         csrc/surface_candidates.hip, surface_thin.hip and nearest_label.hip
+  mesh_io                read_obj / write_obj, read_pcd / write_pcd (numpy only)
+  sample_pointcloud      python -m ogc_amd.data_prepare.sample_pointcloud <data_root> --save_root S [--keep_background]
+  collect_segm           python -m ogc_amd.data_prepare.collect_segm --src_root <OGC-DR root> --dest_root <OGC-DRSV root>
 
 A frame is one upload, crop -> FPS -> labels on the device, one download.  There is no CPU path.
 """
+
+_EXPORTS = {"surface_candidates": "mesh_ops", "surface_thin": "mesh_ops", "nearest_label": "mesh_ops", "sample_surface_even": "mesh_ops",
+            "read_obj": "mesh_io", "write_obj": "mesh_io", "read_pcd": "mesh_io", "write_pcd": "mesh_io"}
+__all__ = sorted(_EXPORTS)
+
+
+def __getattr__(name):
+    # on first use: the drivers above are run as modules and must not find themselves imported already
+    if name in _EXPORTS:
+        import importlib
+        return getattr(importlib.import_module("." + _EXPORTS[name], __name__), name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

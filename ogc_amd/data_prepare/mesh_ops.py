@@ -1,0 +1,193 @@
+"""The device operators of the OGC-DR preparation (csrc/surface_candidates.hip, csrc/surface_thin.hip, csrc/nearest_label.hip;
+DESIGN §4m): random points on mesh surfaces, their thinning to an even sampling, and the label transfer of the single-view set.
+Inputs are CUDA tensors and results stay on the device; the host reads a status word per call (and, in sample_surface_even, the
+areas it needs for the radii, which it computes itself).  There is no CPU path."""
+import numpy as np
+import torch
+
+from .. import pointnet2_cuda as _native
+
+CANDIDATE_STATUS = {1: "a face index outside the vertices", 2: "offsets that do not start at 0, descend or do not end at the array sizes",
+                    3: "a mesh with candidates whose area is not a positive finite number"}
+THIN_STATUS = {1: "a coordinate that is not finite", 2: "a radius that is negative or not finite",
+               3: "cand_offsets that do not start at 0, descend or do not end at the number of points"}
+THIN_FIRST_ROUNDS = 32      # rounds queued before the first read of the status
+THIN_MAX_ROUNDS = 1024      # per call afterwards; every continuation doubles up to here
+
+
+def _check_tensors(tensors):
+    """tensors: (tensor, name, dtype).  Types first, so that a wrong dtype is a TypeError wherever the tensors live."""
+    for t, name, dtype in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype != dtype:
+            raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    for t, name, _ in tensors:
+        if t.device.type != "cuda":
+            raise RuntimeError("%s must be a CUDA tensor (HIP device); ogc_amd has no CPU path" % name)
+
+
+def _check_contiguous(tensors):
+    for t, name, _ in tensors:
+        if not t.is_contiguous():
+            raise RuntimeError("%s must be contiguous" % name)
+
+
+def face_areas(vertices, faces):
+    """numpy: vertices (V, 3) float64, faces (F, 3) integers -> (F,) float64, 0.5 * |cross(v1 - v0, v2 - v0)|: the definition of the
+    areas behind cum_area."""
+    v = np.asarray(vertices, dtype=np.float64)
+    f = np.asarray(faces)
+    return 0.5 * np.linalg.norm(np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]), axis=1)
+
+
+def cumulative_areas(vertices, faces, face_offsets):
+    """numpy: the running sum of the face areas per mesh, restarting at every mesh -> (cum_area (F,) float64, area (M,) float64)."""
+    areas = face_areas(vertices, faces)
+    cum = np.zeros(areas.shape[0], dtype=np.float64)
+    total = np.zeros(len(face_offsets) - 1, dtype=np.float64)
+    for m in range(len(face_offsets) - 1):
+        lo, hi = int(face_offsets[m]), int(face_offsets[m + 1])
+        if hi > lo:
+            cum[lo:hi] = np.cumsum(areas[lo:hi])
+            total[m] = cum[hi - 1]
+    return cum, total
+
+
+def surface_candidates(vertices, faces, cum_area, face_offsets, cand_offsets, seed):
+    """Area-weighted random points on the triangles of M concatenated meshes: vertices (V, 3) fp64, faces (F, 3) int32 indexing
+    them, cum_area (F,) fp64 (cumulative_areas), face_offsets and cand_offsets (M + 1,) int32, CUDA tensors; seed an integer
+    -> (points (C, 3) fp64, face_idx (C,) int32) on the device, C = cand_offsets[-1].  Candidate j of mesh m depends on
+    (seed, m, j) and on its mesh alone (include/ogc_ops.h: ogc_surface_candidates).  One host read: the status word."""
+    tensors = ((vertices, "vertices", torch.float64), (faces, "faces", torch.int32), (cum_area, "cum_area", torch.float64),
+               (face_offsets, "face_offsets", torch.int32), (cand_offsets, "cand_offsets", torch.int32))
+    _check_tensors(tensors)
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be (V, 3), got %s" % (tuple(vertices.shape),))
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces must be (F, 3), got %s" % (tuple(faces.shape),))
+    if tuple(cum_area.shape) != (faces.shape[0],):
+        raise ValueError("cum_area must be (%d,), got %s" % (faces.shape[0], tuple(cum_area.shape)))
+    if face_offsets.dim() != 1 or face_offsets.shape[0] < 1 or tuple(cand_offsets.shape) != tuple(face_offsets.shape):
+        raise ValueError("face_offsets and cand_offsets must both be (M + 1,), got %s and %s"
+                         % (tuple(face_offsets.shape), tuple(cand_offsets.shape)))
+    _check_contiguous(tensors)
+    n_mesh = face_offsets.shape[0] - 1
+    total = int(cand_offsets[-1].item())
+    if total < 0:
+        raise ValueError("cand_offsets ends at %d" % total)
+    points = torch.empty(total, 3, dtype=torch.float64, device=vertices.device)
+    face_idx = torch.empty(total, dtype=torch.int32, device=vertices.device)
+    if total == 0:
+        return points, face_idx
+    status = torch.empty(1, dtype=torch.int32, device=vertices.device)
+    _native.surface_candidates_wrapper(total, n_mesh, vertices.shape[0], faces.shape[0], vertices, faces, cum_area, face_offsets,
+                                       cand_offsets, seed, points, face_idx, status)
+    code = int(status.item())
+    if code:
+        raise ValueError("surface_candidates: " + CANDIDATE_STATUS.get(code, "status %d" % code))
+    return points, face_idx
+
+
+def surface_thin(points, cand_offsets, radius, return_rounds=False):
+    """First-come greedy thinning, exact: points (C, 3) fp64, cand_offsets (M + 1,) int32, radius (M,) fp64, CUDA tensors
+    -> keep (C,) int32 on the device (with return_rounds: and the number of rounds that decided something).
+
+    The definition is sequential and is this package's contract: walking a mesh's candidates in index order, candidate i is kept
+    iff no KEPT candidate j < i of the same mesh has ((dx*dx) + (dy*dy)) + (dz*dz) <= r * r in fp64, the bound inclusive as in
+    cKDTree.query_pairs(r).  It is the rule trimesh.sample.sample_surface_even documents as rejection sampling; trimesh itself is
+    not what the result is pinned to.  Candidates of different meshes never interact.  The device evaluates it in rounds
+    (csrc/surface_thin.hip); the host reads the status once per 32 rounds, then per doubling batch, and continues while
+    candidates are undecided."""
+    tensors = ((points, "points", torch.float64), (cand_offsets, "cand_offsets", torch.int32), (radius, "radius", torch.float64))
+    _check_tensors(tensors)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be (C, 3), got %s" % (tuple(points.shape),))
+    if cand_offsets.dim() != 1 or cand_offsets.shape[0] < 1:
+        raise ValueError("cand_offsets must be (M + 1,), got %s" % (tuple(cand_offsets.shape),))
+    n_mesh = cand_offsets.shape[0] - 1
+    if tuple(radius.shape) != (n_mesh,):
+        raise ValueError("radius must be (%d,), got %s" % (n_mesh, tuple(radius.shape)))
+    _check_contiguous(tensors)
+    total = points.shape[0]
+    keep = torch.empty(total, dtype=torch.int32, device=points.device)
+    if total == 0:
+        return (keep, 0) if return_rounds else keep
+    ws = torch.empty(_native.surface_thin_ws_bytes(total, n_mesh), dtype=torch.uint8, device=points.device)
+    status = torch.empty(3, dtype=torch.int32, device=points.device)
+    rounds, done = THIN_FIRST_ROUNDS, 0
+    while True:
+        _native.surface_thin_wrapper(total, n_mesh, points, cand_offsets, radius, rounds, done, keep, status, ws)
+        done += rounds
+        code, left, used = (int(v) for v in status.cpu())
+        if code:
+            raise ValueError("surface_thin: " + THIN_STATUS.get(code, "status %d" % code))
+        if left == 0:
+            return (keep, used) if return_rounds else keep
+        rounds = min(2 * rounds, THIN_MAX_ROUNDS)
+
+
+def nearest_label(query, source, labels):
+    """Per query point the label and the index of its nearest source point, `labels[cdist(query, source).argmin(1)]`
+    (collect_segm.py:59-61): query (B, Nq, 3), source (B, Ns, 3) fp32, labels (B, Ns) int32, CUDA tensors
+    -> (out_label (B, Nq) int32, out_idx (B, Nq) int32) on the device.  Distances are cdist's fp64 expression; the first index
+    among equal minima wins."""
+    tensors = ((query, "query", torch.float32), (source, "source", torch.float32), (labels, "labels", torch.int32))
+    _check_tensors(tensors)
+    if query.dim() != 3 or query.shape[2] != 3:
+        raise ValueError("query must be (B, Nq, 3), got %s" % (tuple(query.shape),))
+    batch, nq = query.shape[0], query.shape[1]
+    if source.dim() != 3 or source.shape[0] != batch or source.shape[2] != 3:
+        raise ValueError("source must be (%d, Ns, 3), got %s" % (batch, tuple(source.shape)))
+    ns = source.shape[1]
+    if tuple(labels.shape) != (batch, ns):
+        raise ValueError("labels must be (%d, %d), got %s" % (batch, ns, tuple(labels.shape)))
+    if ns < 1 and batch * nq > 0:
+        raise ValueError("source holds no points")
+    _check_contiguous(tensors)
+    out_label = torch.empty(batch, nq, dtype=torch.int32, device=query.device)
+    out_idx = torch.empty(batch, nq, dtype=torch.int32, device=query.device)
+    if batch * nq > 0:
+        _native.nearest_label_wrapper(batch, nq, ns, query, source, labels, out_label, out_idx)
+    return out_label, out_idx
+
+
+def even_radius(area, count):
+    """The radius sample_surface_even thins `3 * count` candidates with: sqrt(area / (3 * count)), float64."""
+    return np.sqrt(np.float64(area) / np.float64(3 * count))
+
+
+def sample_surface_even(vertices, faces, face_offsets, counts, seed):
+    """An even sampling of M concatenated meshes, the package's form of trimesh.sample.sample_surface_even: for every mesh draw
+    3 * count candidates, thin them with the radius sqrt(area / (3 * count)) and keep the first `count` survivors in index order,
+    or all of them if there are fewer.  vertices (V, 3) float64 and faces (F, 3) int32 numpy arrays (the faces index the
+    concatenated vertices), face_offsets (M + 1) and counts (M) integers; seed an integer.
+    -> (points (P, 3) fp64, mesh_idx (P,) int32) CUDA tensors, in mesh order and, inside a mesh, in candidate order.  A mesh whose
+    count is 0 contributes nothing.  One upload of the meshes; the areas are computed on the host (cumulative_areas)."""
+    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+    faces = np.ascontiguousarray(faces, dtype=np.int32)
+    face_offsets = np.asarray(face_offsets, dtype=np.int64)
+    counts = np.asarray(counts, dtype=np.int64)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError("vertices must be (V, 3) and faces (F, 3), got %s and %s" % (vertices.shape, faces.shape))
+    if face_offsets.ndim != 1 or counts.shape != (face_offsets.shape[0] - 1,):
+        raise ValueError("face_offsets must be (M + 1,) and counts (M,), got %s and %s" % (face_offsets.shape, counts.shape))
+    if (counts < 0).any() or 3 * int(counts.sum()) > 1 << 26:
+        raise ValueError("counts must be >= 0 and sum to at most 2**26 / 3")
+    cum, area = cumulative_areas(vertices, faces, face_offsets)
+    cand_offsets = np.concatenate([[0], np.cumsum(3 * counts)]).astype(np.int32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        radius = np.where(counts > 0, even_radius(area, np.maximum(counts, 1)), 0.0)
+    dev = "cuda"
+    cand_dev = torch.from_numpy(cand_offsets).to(dev)
+    points, _ = surface_candidates(torch.from_numpy(vertices).to(dev), torch.from_numpy(faces).to(dev), torch.from_numpy(cum).to(dev),
+                                   torch.from_numpy(face_offsets.astype(np.int32)).to(dev), cand_dev, seed)
+    keep = surface_thin(points, cand_dev, torch.from_numpy(radius).to(dev))
+    # the first `count` survivors of every mesh: a survivor's rank inside its mesh from one running sum
+    mesh_idx = torch.repeat_interleave(torch.arange(counts.shape[0], device=dev, dtype=torch.int32),
+                                       torch.from_numpy(3 * counts).to(dev))
+    running = torch.cumsum(keep, 0, dtype=torch.int64)
+    before = torch.cat([running.new_zeros(1), running])[cand_dev[:-1].long()]       # survivors ahead of each mesh
+    rank = running - before[mesh_idx.long()]                                        # 1-based among the mesh's survivors
+    chosen = (keep == 1) & (rank <= torch.from_numpy(counts).to(dev)[mesh_idx.long()])
+    return points[chosen], mesh_idx[chosen]

@@ -460,6 +460,43 @@ def moving_stats_wrapper(b, total, offsets, pc, flow, segm, semantic_segm, motio
          int(n_ignore), int(ignore_npoint_thresh), float(ground_y), float(moving_thresh), _i(stats, "stats"))
 
 
+def _d(t, name):
+    return _check(t, torch.float64, name)
+
+
+def surface_candidates_wrapper(c, m, v, f, vertices, faces, cum_area, face_offsets, cand_offsets, seed, points, face_idx, status):
+    """c area-weighted random points on the triangles of m concatenated meshes (ogc_surface_candidates): vertices (v, 3) f64,
+    faces (f, 3) i32, cum_area (f,) f64, face_offsets, cand_offsets (m + 1,) i32, seed a 64-bit integer
+    -> points (c, 3) f64, face_idx (c,) i32, status (1,) i32."""
+    seed = int(seed) & 0xffffffffffffffff
+    _run("ogc_surface_candidates", points, c, m, v, f, _d(vertices, "vertices"), _i(faces, "faces"), _d(cum_area, "cum_area"),
+         _i(face_offsets, "face_offsets"), _i(cand_offsets, "cand_offsets"), seed - (1 << 64) if seed >= 1 << 63 else seed,
+         _d(points, "points"), _i(face_idx, "face_idx"), _i(status, "status"))
+
+
+def surface_thin_ws_bytes(c, m):
+    """Bytes of workspace ogc_surface_thin needs for c candidates of m meshes."""
+    n = _lib.load().ogc_surface_thin_ws_bytes(int(c), int(m))
+    if n < 0:
+        raise ValueError("ogc_surface_thin takes at most 2**26 candidates per call, got %d" % c)
+    return n
+
+
+def surface_thin_wrapper(c, m, points, cand_offsets, radius, rounds, rounds_done, keep, status, ws):
+    """Rounds of the first-come greedy thinning (ogc_surface_thin): points (c, 3) f64, cand_offsets (m + 1,) i32, radius (m,) f64,
+    ws a uint8 tensor of surface_thin_ws_bytes(c, m) -> keep (c,) i32, status (3,) i32 = {code, undecided left, rounds used};
+    rounds_done == 0 starts afresh, otherwise the call continues from ws."""
+    _run("ogc_surface_thin", points, c, m, _d(points, "points"), _i(cand_offsets, "cand_offsets"), _d(radius, "radius"), int(rounds),
+         int(rounds_done), _i(keep, "keep"), _i(status, "status"), _check(ws, torch.uint8, "ws"), ws.numel())
+
+
+def nearest_label_wrapper(b, nq, ns, query, source, labels, out_label, out_idx):
+    """Nearest source point and its label per query (ogc_nearest_label): query (b, nq, 3), source (b, ns, 3) f32, labels (b, ns) i32
+    -> out_label, out_idx (b, nq) i32."""
+    _run("ogc_nearest_label", query, b, nq, ns, _f(query, "query"), _f(source, "source"), _i(labels, "labels"), _i(out_label, "out_label"),
+         _i(out_idx, "out_idx"))
+
+
 def png_unfilter(stream_bytes, height, row_bytes, bpp):
     """The row filters of an inflated PNG stream undone on the host (ogc_png_unfilter; nothing is launched): bytes of
     height * (1 + row_bytes) -> numpy uint8 (height, row_bytes)."""

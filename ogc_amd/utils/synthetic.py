@@ -831,3 +831,155 @@ def write_kittisf_raw_root(root, n_frames, height=48, width=160, seed=9300):
         frames.append({"disp1": disp1, "disp2": disp2, "flow": flow, "inst": inst,
                        "P_rect": np.array([float("%.6e" % v) for v in P.reshape(-1)], dtype=np.float32).reshape(3, 4)})
     return frames
+
+
+OGCDR_GROUND_THICKNESS, OGCDR_GROUND_HEIGHT, OGCDR_WALL_THICKNESS = 0.01, -0.5, 0.01      # build_ogcdr.py:55-58
+OGCDR_GROUND_LEVEL = OGCDR_GROUND_HEIGHT + OGCDR_GROUND_THICKNESS
+
+
+def _grid_box(size, k):
+    """A closed box of 12 k^2 triangles around the origin, every side a k x k grid of its own vertices."""
+    import numpy as np
+    size = np.asarray(size, dtype=np.float64)
+    vertices, faces = [], []
+    t = np.linspace(-0.5, 0.5, k + 1)
+    for axis in range(3):
+        for sign in (-0.5, 0.5):
+            a, b = (axis + 1) % 3, (axis + 2) % 3
+            base = len(vertices)
+            for i in range(k + 1):
+                for j in range(k + 1):
+                    p = np.zeros(3)
+                    p[axis], p[a], p[b] = sign, t[i], t[j]
+                    vertices.append(p * size)
+            for i in range(k):
+                for j in range(k):
+                    q = [base + i * (k + 1) + j, base + (i + 1) * (k + 1) + j, base + (i + 1) * (k + 1) + j + 1, base + i * (k + 1) + j + 1]
+                    if sign < 0:
+                        q = q[::-1]
+                    faces += [[q[0], q[1], q[2]], [q[0], q[2], q[3]]]
+    return np.asarray(vertices), faces
+
+
+def _ellipsoid(size, n_around=8, n_rings=6):
+    """A closed ellipsoid of 2 n_around (n_rings - 1) triangles around the origin."""
+    import numpy as np
+    size = np.asarray(size, dtype=np.float64)
+    vertices = [[0.0, 0.5, 0.0]]
+    for r in range(1, n_rings):
+        polar = math.pi * r / n_rings
+        vertices += [[0.5 * math.sin(polar) * math.cos(2 * math.pi * s / n_around), 0.5 * math.cos(polar),
+                      0.5 * math.sin(polar) * math.sin(2 * math.pi * s / n_around)] for s in range(n_around)]
+    vertices.append([0.0, -0.5, 0.0])
+    last = len(vertices) - 1
+    faces = []
+    for s in range(n_around):
+        t = (s + 1) % n_around
+        faces.append([0, 1 + t, 1 + s])
+        for r in range(n_rings - 2):
+            u, v = 1 + r * n_around, 1 + (r + 1) * n_around
+            faces += [[u + s, u + t, v + t], [u + s, v + t, v + s]]
+        faces.append([last, last - n_around + s, last - n_around + t])
+    return np.asarray(vertices) * size, faces
+
+
+def ogcdr_object_mesh(kind, rs):
+    """The canonical mesh of a synthetic OGC-DR object -> (vertices (V, 3) float64, faces: a list of index lists).  kind % 3 == 0: a
+    grid box of 48 triangles with zero-area faces in front, inside and at the end of the list; 1: an ellipsoid of 80 triangles;
+    2: a grid box of 108 triangles, two of them written as one quad."""
+    size = 0.05 + 0.03 * rs.rand(3)
+    if kind % 3 == 0:
+        vertices, faces = _grid_box(size, 2)
+        faces = [[0, 0, 1], [2, 2, 2]] + faces[:20] + [[5, 7, 5]] + faces[20:] + [[3, 4, 4]]
+    elif kind % 3 == 1:
+        vertices, faces = _ellipsoid(size)
+    else:
+        vertices, faces = _grid_box(size, 3)
+        faces = [[faces[0][0], faces[0][1], faces[0][2], faces[1][2]]] + faces[2:]
+    return vertices, faces
+
+
+def box_mesh_between(lo, hi):
+    """The axis-aligned box between two corners as 12 triangles: (vertices (24, 3) float64, faces)."""
+    import numpy as np
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    vertices, faces = _grid_box(hi - lo, 1)
+    return vertices + (lo + hi) / 2, faces
+
+
+def write_ogcdr_mesh_root(root, n_scenes, n_objects=3, n_frames=4, seed=9500, split="val", xz_range=(0.4, 0.3), wall_height=0.08,
+                          meta_key="xz_ground_range"):
+    """`n_scenes` scenes in the layout build_ogcdr.py leaves and sample_pointcloud reads: <root>/mesh/<NN_id>/object_FF_OO.obj — the
+    meshes of ogcdr_object_mesh under a rigid object-to-world pose per frame (a turn about y and a shift of a few millimetres from
+    frame to frame) —, ground.obj and wall_00..03.obj as get_ground / get_walls lay them out around `xz_range` (build_ogcdr.py:370-405)
+    and meta.pkl with the range under `meta_key`; <root>/data/<NN_id>/pose_FF.npy (n_objects, 4, 4) float64 and
+    <root>/data/{train,val,test}.lst, the scenes listed in `split`.  NN is the number of objects.  The room is small, so that at a few
+    thousand sampled points the thinning radius stays below the thickness of ground and walls.  Returns the scene ids."""
+    import os
+    import pickle
+
+    import numpy as np
+
+    from ..data_prepare.mesh_io import write_obj
+    xr = np.asarray(xz_range, dtype=np.float64)
+    ids = []
+    for i in range(n_scenes):
+        rs = np.random.RandomState(seed + i)
+        name = "%02d_%06d" % (n_objects, i)
+        mesh_dir, data_dir = os.path.join(root, "mesh", name), os.path.join(root, "data", name)
+        os.makedirs(mesh_dir, exist_ok=True)
+        os.makedirs(data_dir, exist_ok=True)
+        with open(os.path.join(mesh_dir, "meta.pkl"), "wb") as f:
+            pickle.dump({"room_id": i, "split": split, "n_object": n_objects, meta_key: xr.copy(), "wall_height": float(wall_height)}, f,
+                        protocol=pickle.HIGHEST_PROTOCOL)
+        gl, wt = OGCDR_GROUND_LEVEL, OGCDR_WALL_THICKNESS
+        write_obj(os.path.join(mesh_dir, "ground.obj"), *box_mesh_between([-xr[0] / 2, OGCDR_GROUND_HEIGHT, -xr[1] / 2], [xr[0] / 2, gl, xr[1] / 2]))
+        walls = (([-xr[0] / 2, gl, -xr[1] / 2], [xr[0] / 2, gl + wall_height, -xr[1] / 2 + wt]),
+                 ([-xr[0] / 2, gl, -xr[1] / 2], [-xr[0] / 2 + wt, gl + wall_height, xr[1] / 2]),
+                 ([-xr[0] / 2, gl, xr[1] / 2 - wt], [xr[0] / 2, gl + wall_height, xr[1] / 2]),
+                 ([xr[0] / 2 - wt, gl, -xr[1] / 2], [xr[0] / 2, gl + wall_height, xr[1] / 2]))
+        for w, (lo, hi) in enumerate(walls):
+            write_obj(os.path.join(mesh_dir, "wall_%02d.obj" % w), *box_mesh_between(lo, hi))
+        objects = [ogcdr_object_mesh(k, rs) for k in range(n_objects)]
+        yaw = rs.rand(n_objects) * 2 * math.pi
+        shift = (rs.rand(n_objects, 3) - 0.5) * np.array([xr[0] * 0.4, 0.1, xr[1] * 0.4]) + np.array([0.0, gl + 0.12, 0.0])
+        for t in range(n_frames):
+            poses = np.zeros((n_objects, 4, 4))
+            for k, (vertices, faces) in enumerate(objects):
+                poses[k] = np.eye(4)
+                poses[k, :3, :3], poses[k, :3, 3] = _rot_y_np(yaw[k]), shift[k]
+                write_obj(os.path.join(mesh_dir, "object_%02d_%02d.obj" % (t, k)), _apply_4x4(poses[k], vertices), faces)
+            np.save(os.path.join(data_dir, "pose_%02d.npy" % t), poses)
+            yaw = yaw + (rs.rand(n_objects) - 0.5) * 2 * math.radians(8.0)
+            shift = shift + (rs.rand(n_objects, 3) - 0.5) * np.array([0.016, 0.01, 0.016])
+        ids.append(name)
+    for which in ("train", "val", "test"):
+        with open(os.path.join(root, "data", which + ".lst"), "w") as f:
+            f.write("\n".join(ids) + "\n" if which == split else "")
+    return ids
+
+
+def write_ogcdr_singleview_root(sv_root, complete_root, n_frames=4, seed=9600, jitter=5e-4):
+    """A single-view root for collect_segm from complete clouds: for every scene under <complete_root>/data the file
+    <sv_root>/pcd/<id>/pc_FF.pcd with those points of pc_FF.npy that face +z — at or above the cloud's median z —, each moved by a
+    jitter of `jitter` per coordinate and shuffled, as binary PCD.  Returns {id: [points per frame]}."""
+    import os
+
+    import numpy as np
+
+    from ..data_prepare.mesh_io import write_pcd
+    rs = np.random.RandomState(seed)
+    counts = {}
+    for name in sorted(os.listdir(os.path.join(complete_root, "data"))):
+        src = os.path.join(complete_root, "data", name)
+        if not os.path.isdir(src):
+            continue
+        os.makedirs(os.path.join(sv_root, "pcd", name), exist_ok=True)
+        counts[name] = []
+        for t in range(n_frames):
+            pc = np.load(os.path.join(src, "pc_%02d.npy" % t)).astype(np.float32)
+            view = pc[pc[:, 2] >= np.median(pc[:, 2])]
+            view = (view + (rs.rand(*view.shape).astype(np.float32) - np.float32(0.5)) * np.float32(2 * jitter))[rs.permutation(len(view))]
+            write_pcd(os.path.join(sv_root, "pcd", name, "pc_%02d.pcd" % t), view)
+            counts[name].append(len(view))
+    return counts
