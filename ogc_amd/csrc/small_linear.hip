@@ -62,6 +62,11 @@ __device__ __forceinline__ void sl_tile(int M, int N, int K, const float *__rest
         }
         __syncthreads();
         if (k0 + SL_K < K) sl_fetch(M, N, K, a, am, ak, b, bk, bn, m0, n0, k0 + SL_K, ra, rb);
+        // the row sums (db) slice by slice, then the slice totals: a single accumulator over all K = rows terms rounds the
+        // running total at every term (645 rows of the key / value projection, replayed in fp32 on the host: off by 12 x 2^-24
+        // of the largest element, against 2 x 2^-24 this way and for torch's blocked sum;
+        // tests/test_head_truth_gpu.py::test_module_routes_truth[cross-1032-queries])
+        float ps[2] = {0.f, 0.f};
 #pragma unroll 16
         for (int kk = 0; kk < SL_K; ++kk) {
             const float a0 = As[kk][ty * 2], a1 = As[kk][ty * 2 + 1];
@@ -70,9 +75,11 @@ __device__ __forceinline__ void sl_tile(int M, int N, int K, const float *__rest
             acc[0][1] = fmaf(a0, b1, acc[0][1]);
             acc[1][0] = fmaf(a1, b0, acc[1][0]);
             acc[1][1] = fmaf(a1, b1, acc[1][1]);
-            rs[0] += a0;
-            rs[1] += a1;
+            ps[0] += a0;
+            ps[1] += a1;
         }
+        rs[0] += ps[0];
+        rs[1] += ps[1];
         __syncthreads();
     }
 #pragma unroll
