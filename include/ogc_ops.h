@@ -804,7 +804,18 @@ int ogc_conv1x1_dgrad_adjoint_pooled(int b, int cin, int cout, int hw, int relu,
  *       the dense form up to fp32 summation order.  ogc_conv1x1_dgrad_adjoint_pooled_live writes grad_prev at the positions of
  *       live steps ONLY; ogc_conv1x1_wgrad_moments_first_live / _dgrad_adjoint_first_live read grad_y there only.
  *       nsample in {32, 64}; live_cap (entries per sample of `live`) >= hw / 16, the worst case — n_live stays on the device,
- *       the grids are sized for that case, and workgroups beyond the list leave at once. */
+ *       the grids are sized for that case, and workgroups beyond the list leave at once.
+ *   A level whose first layer is not a first pair (a grouped first layer, then ONE middle layer, then the pooled tail: the second
+ *       level of the segmentation nets) takes the list from the tail down to the middle layer.  The pooled list forms serve its tail
+ *       as they are (cin <= 64, cout <= 128: the adjoint's LDS is the weight tile plus, per wave, (ag, arg) for four entries and
+ *       (c2, c3) once per row — 55.5 KB at cout = 128).  The middle layer has the PLAIN list forms:
+ *       ogc_conv1x1_wgrad_moments_live: ogc_conv1x1_wgrad_moments reading y_prev and grad_y at the positions of live steps only,
+ *       the term of an entry's last position weighted as above.
+ *       ogc_conv1x1_dgrad_adjoint_live_fill: ogc_conv1x1_dgrad_adjoint reading grad_y and y_prev at live positions only and writing
+ *       grad_prev DENSELY — a live position gets the dense form's expression, and the 16 k positions of the k steps an entry skips
+ *       get the value of the entry's last position, which they repeat bit for bit: grad_prev equals the dense form's everywhere, and
+ *       whatever reads it (the grouped first layer's backward) needs no list.  k is clamped to the steps left in the centre: a
+ *       malformed list writes nothing outside the sample. */
 int ogc_live_steps(int b, int p, int nsample, const int *idx, int *live, int *n_live, ogc_stream_t stream);
 int ogc_conv1x1_wgrad_moments_pooled_live(int b, int cin, int cout, int hw, int relu, int nsample, const float *y_prev,
                                           const float *pa, const float *pb, const float *y, const float *coef2,
@@ -814,6 +825,13 @@ int ogc_conv1x1_dgrad_adjoint_pooled_live(int b, int cin, int cout, int hw, int 
                                           const float *coef2, const float *inj, const float *y_prev, const float *pa,
                                           const float *pb, const float *coef, const int *live, const int *n_live, int live_cap,
                                           float *grad_prev, ogc_stream_t stream);
+int ogc_conv1x1_wgrad_moments_live(int b, int cin, int cout, int hw, int relu, int nsample, const float *y_prev, const float *pa,
+                                   const float *pb, const float *grad_y, const int *live, const int *n_live, int live_cap,
+                                   float *moments, ogc_stream_t stream);
+int ogc_conv1x1_dgrad_adjoint_live_fill(int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
+                                        const float *grad_y, const float *y_prev, const float *pa, const float *pb,
+                                        const float *coef, const int *live, const int *n_live, int live_cap, float *grad_prev,
+                                        ogc_stream_t stream);
 int ogc_conv1x1_wgrad_moments_first_live(int b, int cin, int cout, int hw, int relu, int c0, int nsample, const float *x0,
                                          const float *w1, const float *pa, const float *pb, const float *grad_y,
                                          const int *live, const int *n_live, int live_cap, float *moments, ogc_stream_t stream);

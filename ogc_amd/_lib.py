@@ -139,6 +139,9 @@ SIGNATURES = {
                                              _vp],
     "ogc_conv1x1_dgrad_adjoint_first_live": [_int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _int, _vp, _vp],
+    "ogc_conv1x1_wgrad_moments_live": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp],
+    "ogc_conv1x1_dgrad_adjoint_live_fill": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                            _vp],
     "ogc_live_steps_fwd": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_conv1x1_gemm_affine_first_live": [_int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int,
                                            _vp, _vp, _vp],

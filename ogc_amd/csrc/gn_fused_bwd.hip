@@ -512,6 +512,9 @@ void moments_launch(int b, int cin, int cout, int hw, int relu, const AT *x, con
         else if (inj)
             hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, true, AT>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw, chunks,
                                spw, relu, x, dy, pa, pb, c2, ij, s_shift, hm);
+        else if (ls.steps) // (the plain list form: a middle layer behind a pooled tail that wrote dy at live positions only)
+            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
+                               chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm, first, ls);
         else
             hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw, chunks,
                                spw, relu, x, dy, pa, pb, c2, ij, 0, hm);
@@ -605,10 +608,14 @@ __global__ __launch_bounds__(256) void moments_combine_kernel(int b, int cin, in
 // the weight gradient of that convolution, dW1[m][c] = sum_p g_prev[m][p] x0[c][p], which the epilogue forms from the four
 // positions it holds: summed over the 16 lanes of a DPP row, then over the workgroup's run of first.run position tiles in LDS,
 // then one fp32 atomic per element and workgroup into first.dw1.
-// LIST (fp32, POOLED or FIRST): a wave's tile is FOUR ENTRIES of the sample's live-step list (LiveIn above) instead of 64
+// LIST (fp32): a wave's tile is FOUR ENTRIES of the sample's live-step list (LiveIn above) instead of 64
 // consecutive positions — lane j holds positions 4 (j & 3) .. + 3 of entry 4 tile + (j >> 2); the geometry of S = 16, four
-// neighbourhoods per tile, and the pooled table is sized for it.  POOLED writes g_prev at live positions only; FIRST multiplies
-// the term of an entry's last position by the entry's weight and derives the workgroup's run of tiles from the list's length.
+// neighbourhoods per tile, and the pooled table is sized for it (its per-row pair (c2, c3) apart from the per-entry pair (ag, arg):
+// at K = 128 the weight tile and a table of whole float4 would not fit 64 KiB).  POOLED writes g_prev at live positions only; FIRST
+// multiplies the term of an entry's last position by the entry's weight and derives the workgroup's run of tiles from the list's
+// length.  Neither (the plain form, a middle layer between a pooled tail and a layer that reads its gradient densely) reads g_y and
+// y_prev at live positions only and writes g_prev DENSELY: the steps an entry skips (s_shift: log2 of the neighbourhood size,
+// which bounds them) repeat the entry's last position bit for bit, so the four lanes that hold the entry store that value there.
 template <int KQ, bool POOLED, typename AT = float, bool BF = false, int FIRST = 0, bool LIST = false>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M, int K, int hw, int relu,
                                                                            const float *__restrict__ w,     // (K, M)
@@ -638,7 +645,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
     int n_lv = 0;
     const int *lv_ = nullptr;
     if constexpr (LIST) {
-        static_assert((POOLED || FIRST > 0) && !BF && sizeof(AT) == 4, "list form: pooled or first-layer, fp32");
+        static_assert(!BF && sizeof(AT) == 4, "list form: fp32");
         n_lv = min(ls.n[b], ls.cap);
         lv_ = ls.steps + (size_t)b * ls.cap;
         const int tiles = (n_lv + 4 * WG_WAVES - 1) / (4 * WG_WAVES); // a workgroup's tile: 16 entries
@@ -657,12 +664,18 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
     int pos = p0 + 4 * j; // the lane's first position
     bool mine_ok = true;  // LIST: the lane's entry exists (the last tile of a list may hold fewer than four)
     float wl = 1.f;       // LIST: the weight of the lane's LAST position (.w)
+    int skipped = 0;      // LIST, plain form: the steps behind the lane's entry that repeat its last position
     if constexpr (LIST) {
         const int q = 4 * tw + (j >> 2);
         mine_ok = q < n_lv;
         const int ent = lv_[min(q, n_lv - 1)];
-        pos = min(ent & LIVE_MASK, (hw >> 4) - 1) * 16 + 4 * (j & 3);
+        const int step = min(ent & LIVE_MASK, (hw >> 4) - 1);
+        pos = step * 16 + 4 * (j & 3);
         wl = (j & 3) == 3 ? (float)(1 + 16 * (ent >> LIVE_SHIFT)) : 1.f;
+        if constexpr (!POOLED && FIRST == 0) { // (clamped to the steps left in the centre, as the step is clamped to the sample)
+            const int tmask = (1 << (s_shift - 4)) - 1;
+            skipped = mine_ok ? min(max(ent >> LIVE_SHIFT, 0), tmask - (step & tmask)) : 0;
+        }
     }
     const bool lane_live = live && mine_ok;
     float4 x0v[FIRST ? FIRST : 1];
@@ -675,13 +688,18 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
         const int row = q * 4 + kk;
-        xin[q] = (lane_live && q < Kq && row < K) ? ogc_ld4(inb + (size_t)row * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
+        xin[q] = (lane_live && row < K) ? ogc_ld4(inb + (size_t)row * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if (POOLED) {
         // (c2, c3, ag, arg) of the wave's K rows x (64 >> s_shift) neighbourhoods through a wave-private LDS table: read back one
         // 16-byte entry per row right where it is used (held in registers next to the K x 64 tile they cost a wavefront per SIMD)
         const int centres = hw >> s_shift, cpw = LIST ? 4 : 64 >> s_shift; // LIST: one table column per entry of the tile
         float4 *tab = reinterpret_cast<float4 *>(cf + 64 * 5) + (size_t)wave * K * cpw;
+        // LIST: (ag, arg) per row and entry, then (c2, c3) per row — 40 bytes per row and wave instead of 64
+        float2 *tabj = reinterpret_cast<float2 *>(cf + 64 * 5) + (size_t)wave * K * 5, *tabc = tabj + K * 4;
+        if constexpr (LIST) {
+            for (int e = lane; e < K; e += OGC_WAVE) tabc[e] = coef2[(size_t)b * K + e];
+        }
         for (int e = lane; e < K * cpw; e += OGC_WAVE) {
             const int row = e / cpw;
             int centre = (p0 >> s_shift) + (e - row * cpw);
@@ -693,15 +711,22 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
             const float2 cc = coef2[(size_t)b * K + row];
             const float2 jj = (live && centre < centres) ? inj[((size_t)b * K + row) * centres + centre]
                                                          : make_float2(0.f, __int_as_float(-1));
-            tab[e] = make_float4(cc.x, cc.y, jj.x, jj.y);
+            if constexpr (LIST) tabj[e] = jj;
+            else tab[e] = make_float4(cc.x, cc.y, jj.x, jj.y);
         }
         __syncthreads();
         const int mine = LIST ? j >> 2 : (4 * j) >> s_shift, jpos = pos & ((1 << s_shift) - 1);
 #pragma unroll
         for (int q = 0; q < KQ; ++q) { // the expression of gn_maxpool_bwd_dx_kernel, bit for bit (rows beyond K stay zero)
             const int row = q * 4 + kk;
-            if (q < Kq && row < K) {
-                const float4 t = tab[row * cpw + mine];
+            if (row < K) { // (implies q < Kq; one predicate per row keeps the masks of 33 rows out of spilled SGPRs)
+                float4 t;
+                if constexpr (LIST) {
+                    const float2 cc = tabc[row], jj = tabj[row * 4 + mine];
+                    t = make_float4(cc.x, cc.y, jj.x, jj.y);
+                } else {
+                    t = tab[row * cpw + mine];
+                }
                 const int rel = __float_as_int(t.w) - jpos;
                 xin[q].x = fmaf(t.x, xin[q].x, t.y) + (rel == 0 ? t.z : 0.f);
                 xin[q].y = fmaf(t.x, xin[q].y, t.y) + (rel == 1 ? t.z : 0.f);
@@ -835,6 +860,12 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                                 if (j < first.c0) atomicAdd(&s_dw[m * FC_MAX_C0 + j], mine);
                             } else {
                                 if (mine_ok) ogc_st4(outb + (size_t)m * hw + pos, o);
+                                if constexpr (LIST && !POOLED) { // the skipped steps: the value of the entry's last position
+                                    const float v = ogc_dpp_f32<0xFF>(o.w); // (lane 3 of the quad of lanes that holds the entry)
+#pragma unroll
+                                    for (int t = 1; t <= 3; ++t)
+                                        if (t <= skipped) ogc_st4(outb + (size_t)m * hw + pos + 16 * t, make_float4(v, v, v, v));
+                                }
                             }
                         }
                     }
@@ -984,7 +1015,8 @@ int dgrad_adjoint_impl(const char *name, int b, int cin, int cout, int hw, int r
     if (b == 0) return OGC_OK;
     const int M = cin, K = cout, Kq = (K + 3) / 4;
     const size_t lds = ((size_t)64 * ogc_a_ld(Kq) + 64 * 5) * sizeof(float) +
-                       (inj ? (size_t)WG_WAVES * K * (ls.steps ? 4 : 64 >> s_shift) * sizeof(float4) : 0);
+                       (!inj ? 0 : ls.steps ? (size_t)WG_WAVES * K * 5 * sizeof(float2) // (list form: the table's two parts)
+                                            : (size_t)WG_WAVES * K * (64 >> s_shift) * sizeof(float4));
     if (sizeof(AT) == 2 && !ogc_g_matmul_bf16) {
         ogc_set_error("%s: 16-bit activations need ogc_set_matmul_precision(1)", name);
         return OGC_ERR_UNSUPPORTED;
@@ -1008,6 +1040,11 @@ int dgrad_adjoint_impl(const char *name, int b, int cin, int cout, int hw, int r
         if constexpr (sizeof(AT) == 4) {                                                                                    \
             if (inj && ls.steps) { /* (grid of the worst case; workgroups beyond the list leave at once) */                \
                 hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, true, AT, false, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, \
+                                   hw, relu, w, grad_y, y_prev, pa, pb, coef, c2, ij, s_shift, grad_prev, FirstIn(), ls);  \
+                break;                                                                                                      \
+            }                                                                                                               \
+            if (ls.steps) { /* (the plain list form: dense output, s_shift bounds the filled steps) */                     \
+                hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, AT, false, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, \
                                    hw, relu, w, grad_y, y_prev, pa, pb, coef, c2, ij, s_shift, grad_prev, FirstIn(), ls);  \
                 break;                                                                                                      \
             }                                                                                                               \
@@ -1216,6 +1253,31 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_first_live(int b, int cin, int cout, in
     const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
     if (rc != OGC_OK) return rc;
     return dgrad_adjoint_first_impl(name, b, cin, cout, hw, relu, c0, w, grad_y, x0, w1, pa, pb, coef, grad_w1, stream, ls);
+}
+
+// The plain list forms — a middle layer between a pooled tail in list form and a layer that reads its gradient densely: grad_y and
+// y_prev are read at the positions of live steps only, and ogc_conv1x1_dgrad_adjoint_live_fill writes grad_prev densely (a skipped
+// step repeats the last position of the entry that skips it).
+extern "C" int ogc_conv1x1_wgrad_moments_live(int b, int cin, int cout, int hw, int relu, int nsample, const float *y_prev,
+                                              const float *pa, const float *pb, const float *grad_y, const int *live,
+                                              const int *n_live, int live_cap, float *moments, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_wgrad_moments_live";
+    LiveIn ls;
+    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    if (rc != OGC_OK) return rc;
+    return wgrad_moments_impl<float>(name, b, cin, cout, hw, relu, y_prev, pa, pb, grad_y, nullptr, nullptr, 0, moments, stream, ls);
+}
+
+extern "C" int ogc_conv1x1_dgrad_adjoint_live_fill(int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
+                                                   const float *grad_y, const float *y_prev, const float *pa, const float *pb,
+                                                   const float *coef, const int *live, const int *n_live, int live_cap,
+                                                   float *grad_prev, ogc_stream_t stream) {
+    const char *name = "ogc_conv1x1_dgrad_adjoint_live_fill";
+    LiveIn ls;
+    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    if (rc != OGC_OK) return rc;
+    return dgrad_adjoint_impl<float>(name, b, cin, cout, hw, relu, w, grad_y, y_prev, pa, pb, coef, nullptr, nullptr,
+                                     nsample_shift(nsample), grad_prev, stream, ls);
 }
 
 // live (b, p * s / 16), n_live (b): the live-step list of a neighbour list idx (b, p, s) (LiveIn above).

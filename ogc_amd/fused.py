@@ -794,8 +794,12 @@ def _moment_width(t):
     return ACT16_MOMENT_WIDTH if t.dtype is torch.bfloat16 else FUSED_GN_BACKWARD_MAX_WIDTH
 
 
-def _pool_moment_cout(t):
-    return ACT16_MOMENT_WIDTH if t.dtype is torch.bfloat16 else max(FUSED_GN_BACKWARD_MAX_WIDTH, SPARSE_POOL_MAX_COUT)
+def _pool_moment_cout(t, link=None):
+    """Widest pooled tail in moment form; link: the LiveLink of a deeper level's chain whose middle layer took the list."""
+    if t.dtype is torch.bfloat16:
+        return ACT16_MOMENT_WIDTH
+    wide = LIVE_TAIL_MAX_COUT if (link is not None and link.middle and LIVE_DEEP_LEVELS and SKIP_REPEAT_STEPS) else 0
+    return max(FUSED_GN_BACKWARD_MAX_WIDTH, SPARSE_POOL_MAX_COUT, wide)
 
 
 def _norm_act_conv_forward(y_prev, stats_prev, gn_weight, gn_bias, conv_weight, gn_groups, eps, relu, next_groups, pool,
@@ -859,9 +863,17 @@ class _NormActConv(Function):
 
     @staticmethod
     def forward(ctx, y_prev, stats_prev, gn_weight, gn_bias, conv_weight, gn_groups, eps, relu, next_groups, pool=0,
-                next_gamma=None):
+                next_gamma=None, link=None):
         ctx.set_materialize_grads(False)  # no zero tensor (one fill launch per layer) for the statistics output
         y_prev = y_prev.contiguous()
+        # the middle layer of a deeper level (LIVE_DEEP_LEVELS): its backward can walk the live-step list if the pooled tail behind
+        # it does (link.tail, known when the backward pass arrives here) — moment path, fp32, both widths <= 64
+        ctx.link = None
+        if (link is not None and not pool and y_prev.dim() == 4 and y_prev.dtype is torch.float32
+                and link.fits(y_prev.shape[0], y_prev.shape[2], y_prev.shape[3])
+                and _moment_path(y_prev, conv_weight.shape[0], gn_groups) and max(y_prev.shape[1], conv_weight.shape[0]) <= 64
+                and getattr(_api._native, "conv1x1_dgrad_adjoint_live_fill_wrapper", None) is not None):
+            ctx.link, link.middle = link, True
         y, stats, extremes, mean, rstd, a, bb = _norm_act_conv_forward(y_prev, stats_prev, gn_weight, gn_bias, conv_weight,
                                                                        gn_groups, eps, relu, next_groups, pool, next_gamma)
         hw = y_prev.numel() // (y_prev.shape[0] * y_prev.shape[1])
@@ -877,10 +889,11 @@ class _NormActConv(Function):
     @staticmethod
     def backward(ctx, grad_y, _grad_stats=None, *_grad_extremes):
         if grad_y is None:
-            return (None,) * 11
+            return (None,) * 12
         nat = _api._native
         y_prev, gn_weight, gn_bias, conv_weight, mean, rstd, a, bb = ctx.saved_tensors
         gn_groups, relu, hw = ctx.cfg
+        link = ctx.link if (ctx.link is not None and ctx.link.tail) else None   # (else grad_y is dense: the dense walk)
         B, cin = y_prev.shape[0], y_prev.shape[1]
         cout = conv_weight.shape[0]
         grad_y = grad_y.contiguous()
@@ -888,23 +901,31 @@ class _NormActConv(Function):
         grad_w = zeroed_empty((cout, cin), torch.float32, y_prev.device)
         # (up to 64 channels: from 128 on the second accumulator set makes the weight-gradient kernel MFMA-bound and the
         # whole path slower than the separate passes — tools/gn_bwd_compare.py)
-        if (FUSED_GN_BACKWARD and getattr(nat, "conv1x1_dgrad_adjoint_wrapper", None) is not None and hw % 64 == 0
-                and cout <= _moment_width(y_prev) and cin <= _moment_width(y_prev) and gn_groups <= 32
-                and cin % gn_groups == 0):
+        if _moment_path(y_prev, cout, gn_groups):
             # (fp32 operands also under `matmul_precision: bf16`: these layers are HBM-bound, bf16 operands buy nothing here)
             # moment matrices next to the weight gradient -> GroupNorm sums -> adjoint in the input gradient's epilogue:
             # the gradient w.r.t. the normalised activation and both GroupNorm backward passes never touch memory
             dev = y_prev.device
             moments = zeroed_empty((B, 2, cout, cin), torch.float32, dev)
-            nat.conv1x1_wgrad_moments_wrapper(B, cin, cout, hw, relu, y_prev, a, bb, grad_y, moments)
+            if link is not None:   # (grad_y holds live positions only: the tail's list form wrote it)
+                nat.conv1x1_wgrad_moments_live_wrapper(B, cin, cout, hw, relu, y_prev.shape[3], y_prev, a, bb, grad_y, link.live,
+                                                       link.n_live, moments)
+            else:
+                nat.conv1x1_wgrad_moments_wrapper(B, cin, cout, hw, relu, y_prev, a, bb, grad_y, moments)
             coef = torch.empty(B, cin, 3, dtype=torch.float32, device=dev)
             ggb = zeroed_empty((2, cin), torch.float32, dev)
             gw, gb = ggb[0], ggb[1]
             nat.gn_moments_combine_wrapper(B, cin, cout, hw, gn_groups, moments, w.view(cout, cin), a, bb, mean, rstd,
                                            gn_weight.contiguous(), grad_w, coef, gw, gb)
             grad_prev = torch.empty_like(y_prev)
-            nat.conv1x1_dgrad_adjoint_wrapper(B, cin, cout, hw, relu, w.view(cout, cin), grad_y, y_prev, a, bb, coef, grad_prev)
-            return grad_prev, None, gw, gb, grad_w.view_as(conv_weight), None, None, None, None, None, None
+            if link is not None:   # (written everywhere: what reads it takes no list)
+                nat.conv1x1_dgrad_adjoint_live_fill_wrapper(B, cin, cout, hw, relu, y_prev.shape[3], w.view(cout, cin), grad_y, y_prev,
+                                                            a, bb, coef, link.live, link.n_live, grad_prev)
+            else:
+                nat.conv1x1_dgrad_adjoint_wrapper(B, cin, cout, hw, relu, w.view(cout, cin), grad_y, y_prev, a, bb, coef, grad_prev)
+            return grad_prev, None, gw, gb, grad_w.view_as(conv_weight), None, None, None, None, None, None, None
+        if link is not None:
+            raise _live_chain_broken("the middle layer left the moment path")
         nat.conv1x1_wgrad_affine_wrapper(B, cin, cout, hw, relu, y_prev, a, bb, grad_y, grad_w)
         # gradient w.r.t. the (never stored) normalised activation, then through GroupNorm (+ ReLU)
         if y_prev.dtype is torch.bfloat16 or (_gemm_ok(cout, hw) and _plain_gemm_mine(cout, (B, cin, hw))):
@@ -917,7 +938,15 @@ class _NormActConv(Function):
         ws = nat.group_norm_ws(B, cin, gn_groups, True, y_prev.device)
         nat.group_norm_bwd_wrapper(B, cin, hw, gn_groups, relu, y_prev, gn_weight.contiguous(),
                                    gn_bias.contiguous(), mean, rstd, grad_z, grad_prev, gw, gb, ws)
-        return grad_prev, None, gw, gb, grad_w.view_as(conv_weight), None, None, None, None, None, None
+        return grad_prev, None, gw, gb, grad_w.view_as(conv_weight), None, None, None, None, None, None, None
+
+
+def _moment_path(y_prev, cout, gn_groups):
+    """Does _NormActConv.backward go through the moment matrices for this layer?"""
+    cin = y_prev.shape[1]
+    hw = y_prev.numel() // max(y_prev.shape[0] * cin, 1)
+    return (FUSED_GN_BACKWARD and getattr(_api._native, "conv1x1_dgrad_adjoint_wrapper", None) is not None and hw % 64 == 0
+            and cout <= _moment_width(y_prev) and cin <= _moment_width(y_prev) and gn_groups <= 32 and cin % gn_groups == 0)
 
 
 @_gate
@@ -942,14 +971,15 @@ def act16_middle_ok(y_prev, gn, conv):
     return norm_act_conv_available(y_prev, gn, conv) and conv.weight.shape[0] <= 160
 
 
-def norm_act_conv(y_prev, stats_prev, gn, relu, conv, next_gn=None, pool=0):
+def norm_act_conv(y_prev, stats_prev, gn, relu, conv, next_gn=None, pool=0, link=None):
     """(y, stats of y for next_gn or None) = conv(act(gn(y_prev))), see _NormActConv.  pool = nsample (16, 32 or 64) on
     the LAST layer of a set-abstraction MLP, y_prev (B, C, npoint, nsample): a third result, the extremes of y over
-    each neighbourhood for group_norm_act_maxpool (None when the kernel does not offer them for this shape)."""
+    each neighbourhood for group_norm_act_maxpool (None when the kernel does not offer them for this shape).
+    link: the LiveLink of a deeper level whose middle layer this is (LIVE_DEEP_LEVELS), or None."""
     next_groups = next_gn.num_groups if (next_gn is not None and next_gn.affine) else 0
     res = _NormActConv.apply(y_prev, stats_prev, gn.weight, gn.bias, conv.weight, gn.num_groups, gn.eps, bool(relu),
                              next_groups, int(pool) if (pool in (16, 32, 64) and next_groups) else 0,
-                             next_gn.weight if next_groups else None)
+                             next_gn.weight if next_groups else None, link)
     if pool:
         return res[0], res[1], (tuple(res[2:]) if len(res) > 2 else None)
     return res[0], res[1]
@@ -989,17 +1019,46 @@ SKIP_REPEAT_STEPS = True
 LIVE_FORWARD = True
 LIVE_FORWARD_PAIR = True
 
+# ---- ... and the backward of a deeper level ---------------------------------------------------------------------------------------
+# A level whose MLP is grouped first layer -> ONE middle layer -> pooled tail (the second level of the segmentation nets: 1024
+# centres among 2048 points, radius 4, about a third of the 16-column steps live) takes the backward list from the tail down to the
+# middle layer: the tail's two pooled list forms as at a first level, the middle layer's plain list forms
+# (ogc_conv1x1_wgrad_moments_live, ogc_conv1x1_dgrad_adjoint_live_fill).  The middle layer hands a DENSE gradient to the grouped first
+# layer — it fills the skipped steps with the value they repeat — so that node is untouched.  The forward pass stays dense
+# (link.forward is False: no forward list is made).  Taken only when the middle layer AND the tail take it (LiveLink.middle /
+# .tail); off whenever SKIP_REPEAT_STEPS is.  False: the dense walks (tools/step_ab.py LIVE_DEEP_LEVELS).
+LIVE_DEEP_LEVELS = True
+# widest pooled tail of such a chain in moment form.  (SPARSE_POOL_MAX_COUT below stays at 64 for the DENSE forms, where 128 tied in
+# the step; the list forms read a third of what those read.)
+LIVE_TAIL_MAX_COUT = 128
 
-def live_steps(idx):
+
+def deep_chain_wanted(mlp):
+    """plan_live: may this shared MLP (behind a grouped first layer) run as a deeper level's chain?  Three fusable layers, the middle
+    one within the list forms' widths, the tail's output within LIVE_TAIL_MAX_COUT."""
+    if not (LIVE_DEEP_LEVELS and SKIP_REPEAT_STEPS) or len(mlp) != 3:
+        return False
+    convs = []
+    for layer in mlp.children():
+        names = getattr(layer, "_names", None)
+        if names is None or not getattr(layer, "_gn_fuse", False):
+            return False
+        convs.append(getattr(layer, names[0]))
+    c1, c2, c3 = (c.weight.shape[0] for c in convs)
+    return convs[0].weight.shape[1] > FIRST_PAIR_MAX_C0 and max(c1, c2) <= 64 and c3 <= LIVE_TAIL_MAX_COUT
+
+
+def live_steps(idx, forward=True):
     """(live, n_live[, fwd, n_fwd]) of the neighbour lists idx (B, P, S), or None where the list forms would not be taken; the
-    forward list only where the forward list forms may be.  Coordinate-only: part of a level's geometry plan."""
+    forward list only where the forward list forms may be (forward=False: never).  Coordinate-only: part of a level's geometry
+    plan."""
     nat = _api._native
     if not (SKIP_REPEAT_STEPS and torch.is_grad_enabled() and idx is not None and idx.is_cuda and idx.dim() == 3
             and idx.shape[2] in (32, 64) and idx.shape[1] <= 32768 and not deterministic() and getattr(nat, "live_steps_wrapper", None) is not None
             and nat.get_matmul_precision() == "fp32"):
         return None
     idx = (idx if idx.dtype is torch.int32 else idx.int()).contiguous()
-    if (LIVE_FORWARD and (idx.shape[1] * idx.shape[2]) % 64 == 0
+    if (forward and LIVE_FORWARD and (idx.shape[1] * idx.shape[2]) % 64 == 0
             and getattr(nat, "conv1x1_gemm_affine_pool_live_wrapper", None) is not None):
         return nat.live_steps_fwd_wrapper(idx)
     return nat.live_steps_wrapper(idx)
@@ -1008,13 +1067,15 @@ def live_steps(idx):
 class LiveLink:
     """One forward pass of one scale: the live-step lists and what the two nodes of the chain decided (the pair runs first
     forwards, the tail first backwards; each takes the backward list only if the other does).  forward / forward_pair: the tail /
-    the pair as well run their FORWARD list forms — decided for the whole chain by plan_forward before the pair runs."""
-    __slots__ = ("live", "n_live", "fwd", "n_fwd", "pair", "tail", "forward", "forward_pair")
+    the pair as well run their FORWARD list forms — decided for the whole chain by plan_forward before the pair runs.
+    middle: in the pair's place the middle layer of a deeper level (LIVE_DEEP_LEVELS) took the list; such a chain's forward pass is
+    dense."""
+    __slots__ = ("live", "n_live", "fwd", "n_fwd", "pair", "middle", "tail", "forward", "forward_pair")
 
     def __init__(self, live):
         self.live, self.n_live = live[0], live[1]
         self.fwd, self.n_fwd = (live[2], live[3]) if len(live) == 4 else (None, None)
-        self.pair = self.tail = self.forward = self.forward_pair = False
+        self.pair = self.middle = self.tail = self.forward = self.forward_pair = False
 
     def plan_forward(self, x0, conv2, gn2, conv3, gn3):
         """Decide the forward list forms for the chain first pair (x0 -> conv2's output y2) -> pooled tail (gn2, conv3, gn3)."""
@@ -1179,11 +1240,11 @@ class _NormActConvPool(Function):
         y_prev = y_prev.contiguous()
         B, cin, P, S = y_prev.shape
         cout = conv_weight.shape[0]
-        # the live-step list: only behind a first pair that took it (nothing else may read the gradient this node then writes at
-        # live positions only), in moment form, fp32
+        # the live-step list: only behind a first pair, or a deeper level's middle layer, that took it (nothing else may read the
+        # gradient this node then writes at live positions only), in moment form, fp32
         ctx.link = None
-        if (link is not None and link.pair and y_prev.dtype is torch.float32 and link.fits(B, P, S)
-                and cin <= _moment_width(y_prev) and cout <= _pool_moment_cout(y_prev)):
+        if (link is not None and (link.pair or link.middle) and y_prev.dtype is torch.float32 and link.fits(B, P, S)
+                and cin <= _moment_width(y_prev) and cout <= _pool_moment_cout(y_prev, link)):
             ctx.link, link.tail = link, True
         sparse = link is not None and link.forward   # y_prev may hold live positions only, y will
         if sparse and ctx.link is None:
@@ -1223,7 +1284,7 @@ class _NormActConvPool(Function):
         w = conv_weight.contiguous().view(cout, cin)
         # (a chain whose forward ran over live steps never reaches the dense walks below: its ctx.link is set, which implies the
         # moment form's widths)
-        if cin > _moment_width(y_prev) or cout > _pool_moment_cout(y_prev):
+        if ctx.link is None and (cin > _moment_width(y_prev) or cout > _pool_moment_cout(y_prev)):
             # wide tails (SA2 64 -> 128, SA3 128 -> 256 at C4): weight and input gradient rebuild g_y from (y, coef2, inj) while
             # they load y (round 4: ogc_conv1x1_wgrad_affine_pooled, ogc_conv1x1_dgrad_pooled) — the pass that wrote the dense g_y
             # and the two that read it become two that read y; the GroupNorm of y_prev keeps its own backward kernels
@@ -1261,9 +1322,10 @@ class _NormActConvPool(Function):
 
 
 @_gate
-def norm_act_conv_pool_available(y_prev, gn, conv, next_gn):
+def norm_act_conv_pool_available(y_prev, gn, conv, next_gn, link=None):
     """Can the last layer of a set-abstraction MLP and its pooled GroupNorm run as _NormActConvPool?  (The shapes for which
-    _NormActConv takes the extremes path forwards and the moment-matrix path backwards.)"""
+    _NormActConv takes the extremes path forwards and the moment-matrix path backwards.)  link: the LiveLink of a deeper level's
+    chain — its tail takes the moment form up to LIVE_TAIL_MAX_COUT, in list form."""
     nat = _api._native
     if not (SPARSE_POOL_BACKWARD and FUSED_GN_BACKWARD and y_prev.dim() == 4 and y_prev.shape[-1] in (16, 32, 64)
             and next_gn is not None and next_gn.affine and norm_act_conv_available(y_prev, gn, conv)
@@ -1271,6 +1333,13 @@ def norm_act_conv_pool_available(y_prev, gn, conv, next_gn):
             and getattr(nat, "conv1x1_gemm_affine_pool_wrapper", None) is not None):
         return False
     cin, cout, g, g2 = y_prev.shape[1], conv.weight.shape[0], gn.num_groups, next_gn.num_groups
+    if (link is not None and link.middle and y_prev.dtype is torch.float32 and cin <= _moment_width(y_prev)
+            and cout <= _pool_moment_cout(y_prev, link) and link.fits(y_prev.shape[0], y_prev.shape[2], y_prev.shape[3])):
+        # LDS of ogc_conv1x1_dgrad_adjoint_pooled_live: the weight tile + per wave and output channel (ag, arg) of four entries
+        # and one (c2, c3)
+        lds = (64 * 4 * (((cout + 3) // 4) | 1) + 320) * 4 + 4 * cout * 40
+        return (lds <= 65536 and (y_prev.shape[2] * y_prev.shape[3]) % 64 == 0 and g <= 32 and cin % g == 0
+                and g2 <= 32 and cout % g2 == 0 and (cout // g2) % 4 == 0)
     if cin > _moment_width(y_prev) or cout > _pool_moment_cout(y_prev):
         # wide tails: the pooled forms of the plain weight / input gradient kernels (fp32 operands, enough position tiles for
         # the chunked kernel, neighbourhood extremes from the forward convolution)

@@ -923,6 +923,20 @@ def conv1x1_dgrad_adjoint_first_live_wrapper(b, cin, cout, hw, relu, c0, nsample
          _f(grad_w1, "grad_w1"))
 
 
+def conv1x1_wgrad_moments_live_wrapper(b, cin, cout, hw, relu, nsample, y_prev, pa, pb, grad_y, live, n_live, moments):
+    """conv1x1_wgrad_moments_wrapper (fp32) over the live-step list: y_prev and grad_y are read at the positions of live steps only."""
+    _run("ogc_conv1x1_wgrad_moments_live", y_prev, b, cin, cout, hw, int(relu), nsample, _f(y_prev, "y_prev"), _f(pa, "pa"),
+         _f(pb, "pb"), _f(grad_y, "grad_y"), *_live_args(live, n_live), _f(moments, "moments"))
+
+
+def conv1x1_dgrad_adjoint_live_fill_wrapper(b, cin, cout, hw, relu, nsample, w, grad_y, y_prev, pa, pb, coef, live, n_live,
+                                            grad_prev):
+    """conv1x1_dgrad_adjoint_wrapper (fp32) over the live-step list: grad_y and y_prev are read at the positions of live steps
+    only, grad_prev is written everywhere (a skipped step repeats the last position of the entry that skips it)."""
+    _run("ogc_conv1x1_dgrad_adjoint_live_fill", grad_y, b, cin, cout, hw, int(relu), nsample, _f(w, "w"), _f(grad_y, "grad_y"),
+         _f(y_prev, "y_prev"), _f(pa, "pa"), _f(pb, "pb"), _f(coef, "coef"), *_live_args(live, n_live), _f(grad_prev, "grad_prev"))
+
+
 def live_steps_fwd_wrapper(idx):
     """(live, n_live) as live_steps_wrapper, and (fwd, n_fwd): the same entries packed for the forward list forms — no group
     of one 64-position tile crosses a tile of four entries, empty slots hold -1 (ogc_live_steps_fwd)."""

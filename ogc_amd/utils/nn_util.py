@@ -173,11 +173,16 @@ def _shared_mlp_run(self, x, pool, first=None, live=None):
     last layer's norm / activation (/ max over the neighbourhood, `pool`) is one fused op.
     first: optional callable (conv, gn) -> (raw output, statistics) that evaluates the FIRST layer's convolution (a set-
     abstraction level fuses it with the grouping, fused.grouped_first_layer); `x` is then unused.
-    live: optional live-step list of the level's neighbour lists (fused.live_steps) for a first pair followed by a pooled tail."""
+    live: optional live-step list of the level's neighbour lists (fused.live_steps) for a first pair followed by a pooled tail, or
+    (with `first`) for the middle layer and the pooled tail of a deeper level (fused.LIVE_DEEP_LEVELS)."""
     from ..fused import (act16_middle_ok, group_norm_act, group_norm_act_maxpool, norm_act_conv, norm_act_conv_available,
                          norm_act_conv_pool, norm_act_conv_pool_available, pointwise_conv)
     layers = list(self.children())
     link = None   # the live-step list on its way from the first pair to the pooled tail directly behind it
+    deep = first is not None and live is not None and bool(pool) and len(layers) == 3   # a deeper level's chain: middle layer -> tail
+    if deep:
+        from ..fused import LiveLink
+        link = LiveLink(live)
     pending = None  # (raw conv output, its GroupNorm statistics or None, the GroupNorm, relu?, neighbourhood extremes)
 
     def flush(p, last):
@@ -238,10 +243,10 @@ def _shared_mlp_run(self, x, pool, first=None, live=None):
             if pool and li == len(layers) - 1 and pending[0].dim() == 4 and pending[0].shape[-1] in (16, 32, 64):
                 # last layer before the max over the neighbourhood: the convolution also leaves each neighbourhood's
                 # extremes, from which the pooled activation follows without reading its output again
-                if norm_act_conv_pool_available(pending[0], pending[2], conv, gn):
+                tail_link = link if li == 2 else None
+                if norm_act_conv_pool_available(pending[0], pending[2], conv, gn, tail_link):
                     # ... and one autograd node for the whole tail: no dense gradient between the pooling and the convolution
-                    return norm_act_conv_pool(pending[0], pending[1], pending[2], pending[3], conv, gn, relu,
-                                              link if li == 2 else None)
+                    return norm_act_conv_pool(pending[0], pending[1], pending[2], pending[3], conv, gn, relu, tail_link)
             if link is not None and link.forward_pair:   # (plan_forward asked the same questions: not reached)
                 raise RuntimeError("first level over live steps: the tail does not run as one pooled node, and the pair's output "
                                    "is valid at live positions only")
@@ -249,7 +254,9 @@ def _shared_mlp_run(self, x, pool, first=None, live=None):
                 y, stats, extremes = norm_act_conv(pending[0], pending[1], pending[2], pending[3], conv, gn,
                                                    pool=pending[0].shape[-1])
             else:
-                y, stats = norm_act_conv(pending[0], pending[1], pending[2], pending[3], conv, gn)
+                # (the middle layer of a deeper level's chain: it takes the list backwards if the pooled tail behind it does)
+                y, stats = norm_act_conv(pending[0], pending[1], pending[2], pending[3], conv, gn,
+                                         link=link if (deep and li == 1) else None)
         else:
             if link is not None and link.forward_pair:
                 raise RuntimeError("first level over live steps: the tail cannot fold the norm into its convolution, and the "

@@ -41,13 +41,24 @@ class _PointnetSAModuleBase(nn.Module):
 
     def plan_live(self, idx):
         """The live-step list of every scale whose MLP can run as first pair + pooled tail (three layers on a narrow grouped
-        input: fused.SKIP_REPEAT_STEPS), for the backward kernels of that chain; only where a gradient will be asked for."""
+        input: fused.SKIP_REPEAT_STEPS), for the backward kernels of that chain; only where a gradient will be asked for.  A scale
+        whose MLP is grouped first layer + one middle layer + pooled tail (fused.LIVE_DEEP_LEVELS) gets the backward list alone:
+        its forward pass stays dense."""
         from .. import fused as _fused
 
         def chain(mlp):
             head = mlp.first_layer() if len(mlp) == 3 else None
             return head is not None and head[0].weight.shape[1] <= _fused.FIRST_PAIR_MAX_C0
-        return [_fused.live_steps(j) if (j is not None and chain(mlp)) else None for j, mlp in zip(idx, self.mlps)]
+
+        def plan(j, mlp):
+            if j is None:
+                return None
+            if chain(mlp):
+                return _fused.live_steps(j)
+            if _fused.deep_chain_wanted(mlp):
+                return _fused.live_steps(j, forward=False)
+            return None
+        return [plan(j, mlp) for j, mlp in zip(idx, self.mlps)]
 
     def plan_reverse(self, idx, n):
         """Transposed neighbour lists (which (centre, slot) positions point at each source point) of every scale, for the
@@ -116,7 +127,8 @@ class _PointnetSAModuleBase(nn.Module):
                     # grouping + first convolution without the (B, 3 + C, npoint, nsample) tensor in between
                     pooled.append(mlp.forward_maxpool(None, first=lambda conv, gn, j=nn_idx, rv=geometry["rev"][i]:
                                                       grouped_first_layer(xyz, new_xyz, features, j, conv, gn, rv,
-                                                                          act16=len(mlp) >= 2)))
+                                                                          act16=len(mlp) >= 2),
+                                                      live=geometry["live"][i]))
                     continue
                 grouped = grouper(xyz, new_xyz, features, idx=nn_idx)[0]
                 pooled.append(mlp.forward_maxpool(grouped, live=geometry["live"][i]))
