@@ -55,7 +55,7 @@ enum {
  * ogc_soft_carry likewise: a new entry point, no prototype changed.  ogc_scan_crop_camera / _front / _tile and ogc_box_segm /
  * _chunk likewise.  ogc_kittisf_unproject and ogc_png_unfilter likewise.  ogc_live_steps_fwd, ogc_conv1x1_gemm_affine_first_live
  * and ogc_conv1x1_gemm_affine_pool_live likewise.  ogc_moving_stats / _label_cap likewise.  ogc_surface_candidates, ogc_surface_thin /
- * _ws_bytes and ogc_nearest_label likewise. */
+ * _ws_bytes and ogc_nearest_label likewise.  ogc_depth_render / _ws_bytes / _timed and ogc_depth_points likewise. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -696,6 +696,52 @@ int ogc_surface_thin(int C, int M, const double *points, const int *cand_offsets
  * 32-bit indexing of the coordinates, a null pointer: OGC_ERR_INVALID_ARG, nothing launched. */
 int ogc_nearest_label(int B, int Nq, int Ns, const float *query, const float *source, const int *labels, int *out_label, int *out_idx,
                       ogc_stream_t stream);
+
+/* Depth render of triangle meshes and the cloud of its hit points (csrc/depth_render.hip): the device stage of the
+ * OGC-DRSV preparation, what data_prepare/ogcdrsv/build_ogcdrsv.py obtains from open3d's visualiser.  The definition below is THIS
+ * package's contract; open3d's rasteriser is not what the result is pinned to.  All arithmetic is fp64, one rounding per operation,
+ * nothing contracted, sums left to right; tests/depth_render_cases.py repeats the sequence in numpy.
+ *
+ * view: OGC_DEPTH_VIEW_DOUBLES doubles in HOST memory, read before the call returns: eye e (3), right (3), up (3), back (3) — an
+ * orthonormal frame the caller vouches for, the camera looks along -back —, focal length f in pixels, principal point cx, cy, near,
+ * far.  All finite, f > 0, 0 < near <= far, otherwise OGC_ERR_INVALID_ARG.  The image is width x height, row 0 the top row; pixel (x, y)
+ * has its centre q = (x + 0.5, y + 0.5) and the row-major number y * width + x.
+ *   camera     d = p - e;  xc = (right0*d0 + right1*d1) + right2*d2,  yc likewise with up,  zc = -((back0*d0 + back1*d1) + back2*d2)
+ *   screen     sx = cx + f * (xc / zc),  sy = cy - f * (yc / zc)
+ *   near       a face with a vertex at zc < near is dropped whole and counted in status[2]; nothing is clipped
+ *   empty      a face with a non-finite camera or screen coordinate, or whose screen area
+ *              (s1x - s0x) * (s2y - s0y) - (s1y - s0y) * (s2x - s0x) is exactly 0, covers nothing
+ *   coverage   the three edge functions (bx - ax) * (qy - ay) - (by - ay) * (qx - ax) over (a, b) = (s0, s1), (s1, s2), (s2, s0):
+ *              q is covered iff all three are >= 0 or all three are <= 0 — inclusive and two-sided, nothing is culled — and q lies in
+ *              the closed bounding interval of the three screen vertices in x and in y.  A centre on an edge two faces share belongs
+ *              to both; the depth test settles it.
+ *   depth      n = cross(c1 - c0, c2 - c0) of the camera coordinates c = (xc, yc, zc), each component a * b - c * d;
+ *              nc0 = (nx*c0x + ny*c0y) + nz*c0z;  the ray g = ((qx - cx) / f, -((qy - cy) / f), 1);  ng = (nx*gx + ny*gy) + nz;
+ *              no hit when ng == 0;  t = nc0 / ng, no hit when t is not finite;  t is clamped into [min zc, max zc] of the face's
+ *              three vertices;  the hit is kept iff near <= t <= far
+ *   winner     the smallest t wins the pixel; among faces with that t, the lowest face index
+ *   point      per coordinate k:  e_k + t * ((gx * right_k + gy * up_k) - back_k), rounded to fp32 last
+ * ogc_depth_render: vertices (V, 3) f64, faces (F, 3) i32 -> depth (height, width) f64, +inf where no face is hit, and
+ * face (height, width) i32, -1 there.  status (3) i32 out: {code, (P, written by ogc_depth_points), faces dropped by the near rule}.
+ * code: 0, or 1 a face index outside [0, V), 2 a face with a vertex coordinate that is not finite (the larger code if both occur);
+ * with a code set depth and face are not written.  F == 0 gives the empty image.  The image is the same in every run: both stages
+ * take minima with integer atomics (csrc/depth_render.hip).  ws: ws_bytes >= ogc_depth_render_ws_bytes(F) bytes, 256-byte aligned
+ * (not needed when F == 0).  F > 2^24: OGC_ERR_UNSUPPORTED.  Negative sizes, a side of the image outside [1, 16384], a view as above,
+ * a null pointer, a small or misaligned workspace: OGC_ERR_INVALID_ARG.  Nothing launched.
+ * ogc_depth_points: the covered pixels of depth and face (same view, same status buffer, after ogc_depth_render on the same stream)
+ * as a stable compaction in row-major pixel order: points (P, 3) f32, pixel (P) i32 the pixel's number, face_out (P) i32; the three
+ * buffers have room for width * height rows.  status[1] = P.  With status[0] != 0 nothing is written. */
+#define OGC_DEPTH_VIEW_DOUBLES 17
+long long ogc_depth_render_ws_bytes(int F); /* -1 for an F outside [0, 2^24] */
+int ogc_depth_render(int V, int F, const double *vertices, const int *faces, const double *view, int width, int height, double *depth,
+                     int *face, int *status, void *ws, long long ws_bytes, ogc_stream_t stream);
+int ogc_depth_points(int width, int height, const double *view, const double *depth, const int *face, float *points, int *pixel,
+                     int *face_out, int *status, ogc_stream_t stream);
+/* ogc_depth_render_timed: ogc_depth_render with HIP events around its three stages, for tools/ogcdrsv_render_time.py.  Unlike every
+ * other launching entry point it WAITS, for its last event: stage_ms (3 floats, HOST memory) = milliseconds of {setup: status, face
+ * records, item offsets, the empty image; the depth pass; the face pass}.  Same results, same refusals. */
+int ogc_depth_render_timed(int V, int F, const double *vertices, const int *faces, const double *view, int width, int height,
+                           double *depth, int *face, int *status, void *ws, long long ws_bytes, float *stage_ms, ogc_stream_t stream);
 
 /* Attention core of the MaskFormer head's nn.MultiheadAttention layers
  *   utils/transformer_util.py:5-62 (cross-attention slots <- points, self-attention among the slots; 8 heads,

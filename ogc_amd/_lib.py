@@ -96,6 +96,10 @@ SIGNATURES = {
     "ogc_surface_thin_ws_bytes": [_int, _int],
     "ogc_surface_thin": [_int, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _ll, _vp],
     "ogc_nearest_label": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_depth_render_ws_bytes": [_int],
+    "ogc_depth_render": [_int, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _ll, _vp],
+    "ogc_depth_render_timed": [_int, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _ll, _vp, _vp],
+    "ogc_depth_points": [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_concat": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_fwd": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_bwd": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -228,6 +232,7 @@ def load():
         L.ogc_cell_grid_bytes.restype = ctypes.c_longlong
         L.ogc_sup_loss_ws_doubles.restype = ctypes.c_longlong
         L.ogc_surface_thin_ws_bytes.restype = ctypes.c_longlong
+        L.ogc_depth_render_ws_bytes.restype = ctypes.c_longlong
         L.ogc_last_error.restype = ctypes.c_char_p
         L.ogc_set_deterministic(1 if DETERMINISTIC else 0)
         _lib = L

@@ -18,11 +18,14 @@ the readers of ogc_amd/datasets.py load.
   mesh_io                read_obj / write_obj, read_pcd / write_pcd (numpy only)
   sample_pointcloud      python -m ogc_amd.data_prepare.sample_pointcloud <data_root> --save_root S [--keep_background]
   collect_segm           python -m ogc_amd.data_prepare.collect_segm --src_root <OGC-DR root> --dest_root <OGC-DRSV root>
+  build_ogcdrsv          python -m ogc_amd.data_prepare.build_ogcdrsv --src_root <OGC-DR root> --dest_root <OGC-DRSV root>
+                         (mesh_ops.default_view / depth_render / render_points over csrc/depth_render.hip)
 
 A frame is one upload, crop -> FPS -> labels on the device, one download.  There is no CPU path.
 """
 
 _EXPORTS = {"surface_candidates": "mesh_ops", "surface_thin": "mesh_ops", "nearest_label": "mesh_ops", "sample_surface_even": "mesh_ops",
+            "default_view": "mesh_ops", "depth_render": "mesh_ops", "render_points": "mesh_ops",
             "read_obj": "mesh_io", "write_obj": "mesh_io", "read_pcd": "mesh_io", "write_pcd": "mesh_io"}
 __all__ = sorted(_EXPORTS)
 

@@ -1,7 +1,12 @@
 """The device operators of the OGC-DR preparation (csrc/surface_candidates.hip, csrc/surface_thin.hip, csrc/nearest_label.hip;
 DESIGN §4m): random points on mesh surfaces, their thinning to an even sampling, and the label transfer of the single-view set.
 Inputs are CUDA tensors and results stay on the device; the host reads a status word per call (and, in sample_surface_even, the
-areas it needs for the radii, which it computes itself).  There is no CPU path."""
+areas it needs for the radii, which it computes itself).  There is no CPU path.
+The depth render of the OGC-DRSV preparation (csrc/depth_render.hip) is here too: default_view, depth_render and
+render_points."""
+import collections
+import math
+
 import numpy as np
 import torch
 
@@ -150,6 +155,119 @@ def nearest_label(query, source, labels):
     if batch * nq > 0:
         _native.nearest_label_wrapper(batch, nq, ns, query, source, labels, out_label, out_idx)
     return out_label, out_idx
+
+
+RENDER_STATUS = {1: "a face index outside the vertices", 2: "a vertex coordinate that is not finite"}
+
+View = collections.namedtuple("View", "e right up back f cx cy near far")
+View.__doc__ = """A pinhole view (include/ogc_ops.h: ogc_depth_render): eye e, the orthonormal right, up and back (the camera looks along
+-back), focal length f in pixels, principal point (cx, cy), near and far.  Plain Python floats; the library receives doubles."""
+
+
+def view_doubles(view):
+    """The 17 doubles of a View in the order the library takes them."""
+    vals = [float(x) for x in (*view.e, *view.right, *view.up, *view.back, view.f, view.cx, view.cy, view.near, view.far)]
+    if len(vals) != _native.DEPTH_VIEW_DOUBLES:
+        raise ValueError("e, right, up and back are 3 numbers each")
+    return vals
+
+
+def default_view(lo, hi, width=1920, height=1080, fov_deg=60, zoom=0.7, **fields):
+    """The view build_ogcdrsv renders a frame with, from the bounding box [lo, hi] of the rendered vertices: lookat the centre of the
+    box, front (0, 0, 1), up (0, 1, 0), ext the longest edge, distance = zoom * ext / tan(fov / 2), the eye at lookat + front *
+    distance, the field of view vertical: f = (height / 2) / tan(fov / 2), the principal point the image centre,
+    near = max(0.01 * ext, distance - 3 * ext), far = distance + 3 * ext.  It restates open3d's ViewControl defaults as far as they
+    are known and has NOT been compared with open3d.  Any field of View can be given by keyword and then replaces the default.  The
+    trigonometry runs here, in Python floats."""
+    lo = [float(x) for x in lo]
+    hi = [float(x) for x in hi]
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(a) and math.isfinite(b) and a <= b for a, b in zip(lo, hi)):
+        raise ValueError("lo and hi must be 3 finite numbers each with lo <= hi, got %s and %s" % (lo, hi))
+    if width < 1 or height < 1 or not 0.0 < fov_deg < 180.0 or not zoom > 0.0:
+        raise ValueError("width and height must be >= 1, fov_deg in (0, 180) and zoom > 0")
+    ext = max(h - l for l, h in zip(lo, hi))
+    if not ext > 0.0:
+        raise ValueError("the bounding box has no extent")
+    tan_half = math.tan(math.radians(fov_deg) / 2.0)
+    distance = zoom * ext / tan_half
+    lookat = [(l + h) / 2.0 for l, h in zip(lo, hi)]
+    view = View(e=(lookat[0], lookat[1], lookat[2] + distance), right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), back=(0.0, 0.0, 1.0),
+                f=(height / 2.0) / tan_half, cx=width / 2.0, cy=height / 2.0, near=max(0.01 * ext, distance - 3.0 * ext),
+                far=distance + 3.0 * ext)
+    unknown = set(fields) - set(View._fields)
+    if unknown:
+        raise TypeError("default_view: unknown fields %s" % sorted(unknown))
+    return view._replace(**fields)
+
+
+def _check_mesh(vertices, faces):
+    tensors = ((vertices, "vertices", torch.float64), (faces, "faces", torch.int32))
+    _check_tensors(tensors)
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be (V, 3), got %s" % (tuple(vertices.shape),))
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces must be (F, 3), got %s" % (tuple(faces.shape),))
+    _check_contiguous(tensors)
+
+
+def _check_image(width, height):
+    if not (1 <= int(width) <= 16384 and 1 <= int(height) <= 16384):
+        raise ValueError("width and height must be in 1..16384, got %s x %s" % (width, height))
+    return int(width), int(height)
+
+
+def _render(vertices, faces, doubles, width, height):
+    depth = torch.empty(height, width, dtype=torch.float64, device=vertices.device)
+    face = torch.empty(height, width, dtype=torch.int32, device=vertices.device)
+    status = torch.empty(3, dtype=torch.int32, device=vertices.device)
+    ws = torch.empty(_native.depth_render_ws_bytes(faces.shape[0]), dtype=torch.uint8, device=vertices.device)
+    _native.depth_render_wrapper(vertices.shape[0], faces.shape[0], vertices, faces, doubles, width, height, depth, face, status, ws)
+    return depth, face, status
+
+
+def _render_status(name, status):
+    code, count, dropped = (int(v) for v in status.cpu())
+    if code:
+        raise ValueError("%s: %s" % (name, RENDER_STATUS.get(code, "status %d" % code)))
+    return count, dropped
+
+
+def depth_render(vertices, faces, view, width, height, return_dropped=False):
+    """The depth image of triangle meshes through a View (include/ogc_ops.h: ogc_depth_render): vertices (V, 3) fp64, faces (F, 3)
+    int32, CUDA tensors -> (depth (height, width) fp64, +inf where nothing is hit, face (height, width) int32, -1 there) on the device;
+    with return_dropped also the number of faces the near rule dropped.  The nearest hit wins a pixel, the lowest face index among
+    equal depths.  One host read: the status."""
+    _check_mesh(vertices, faces)
+    width, height = _check_image(width, height)
+    depth, face, status = _render(vertices, faces, view_doubles(view), width, height)
+    _, dropped = _render_status("depth_render", status)
+    return (depth, face, dropped) if return_dropped else (depth, face)
+
+
+def render_points(vertices, faces, view, width, height, face_offsets=None):
+    """The cloud a depth render sees: the hit points of the covered pixels in row-major pixel order (ogc_depth_render, then
+    ogc_depth_points) -> (points (P, 3) fp32, pixel (P,) int32 = y * width + x, face (P,) int32) on the device, and with
+    face_offsets ((M + 1,) int32 CUDA tensor, ascending from 0 to F) also mesh_idx (P,) int32, the mesh of each point's face.
+    One host read for both stages: the status, which carries P."""
+    _check_mesh(vertices, faces)
+    if face_offsets is not None:
+        _check_tensors(((face_offsets, "face_offsets", torch.int32),))
+        if face_offsets.dim() != 1 or face_offsets.shape[0] < 1:
+            raise ValueError("face_offsets must be (M + 1,), got %s" % (tuple(face_offsets.shape),))
+        _check_contiguous(((face_offsets, "face_offsets", torch.int32),))
+    width, height = _check_image(width, height)
+    doubles = view_doubles(view)
+    depth, face, status = _render(vertices, faces, doubles, width, height)
+    points = torch.empty(width * height, 3, dtype=torch.float32, device=vertices.device)
+    pixel = torch.empty(width * height, dtype=torch.int32, device=vertices.device)
+    face_out = torch.empty(width * height, dtype=torch.int32, device=vertices.device)
+    _native.depth_points_wrapper(width, height, doubles, depth, face, points, pixel, face_out, status)
+    count, _ = _render_status("render_points", status)
+    points, pixel, face_out = points[:count], pixel[:count], face_out[:count]
+    if face_offsets is None:
+        return points, pixel, face_out
+    mesh_idx = (torch.searchsorted(face_offsets, face_out, right=True) - 1).to(torch.int32)
+    return points, pixel, face_out, mesh_idx
 
 
 def even_radius(area, count):

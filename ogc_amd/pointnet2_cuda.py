@@ -497,6 +497,49 @@ def nearest_label_wrapper(b, nq, ns, query, source, labels, out_label, out_idx):
          _i(out_idx, "out_idx"))
 
 
+DEPTH_VIEW_DOUBLES = 17    # OGC_DEPTH_VIEW_DOUBLES: e, right, up, back (3 each), f, cx, cy, near, far
+
+
+def _view(view):
+    import ctypes
+    vals = [float(x) for x in view]
+    if len(vals) != DEPTH_VIEW_DOUBLES:
+        raise ValueError("a view is %d doubles (e, right, up, back, f, cx, cy, near, far), got %d" % (DEPTH_VIEW_DOUBLES, len(vals)))
+    return (ctypes.c_double * DEPTH_VIEW_DOUBLES)(*vals)
+
+
+def depth_render_ws_bytes(f):
+    """Bytes of workspace ogc_depth_render needs for f faces."""
+    n = _lib.load().ogc_depth_render_ws_bytes(int(f))
+    if n < 0:
+        raise ValueError("ogc_depth_render takes at most 2**24 faces per call, got %d" % f)
+    return n
+
+
+def depth_render_wrapper(v, f, vertices, faces, view, width, height, depth, face, status, ws):
+    """Depth render (ogc_depth_render): vertices (v, 3) f64, faces (f, 3) i32, view 17 host doubles, ws a uint8 tensor of
+    depth_render_ws_bytes(f) -> depth (height, width) f64, face (height, width) i32, status (3,) i32 = {code, -, dropped_near}."""
+    _run("ogc_depth_render", depth, v, f, _d(vertices, "vertices"), _i(faces, "faces"), _view(view), int(width), int(height),
+         _d(depth, "depth"), _i(face, "face"), _i(status, "status"), _check(ws, torch.uint8, "ws"), ws.numel())
+
+
+def depth_render_timed_wrapper(v, f, vertices, faces, view, width, height, depth, face, status, ws):
+    """depth_render_wrapper through ogc_depth_render_timed, which waits for its launches -> milliseconds of (setup, depth pass, face
+    pass) by HIP events.  For the timing tool."""
+    import ctypes
+    stage_ms = (ctypes.c_float * 3)()
+    _run("ogc_depth_render_timed", depth, v, f, _d(vertices, "vertices"), _i(faces, "faces"), _view(view), int(width), int(height),
+         _d(depth, "depth"), _i(face, "face"), _i(status, "status"), _check(ws, torch.uint8, "ws"), ws.numel(), stage_ms)
+    return tuple(stage_ms)
+
+
+def depth_points_wrapper(width, height, view, depth, face, points, pixel, face_out, status):
+    """The covered pixels of a depth render in row-major order (ogc_depth_points): depth (height, width) f64, face (height, width)
+    i32 -> points (width * height, 3) f32, pixel, face_out (width * height,) i32, the first status[1] rows written."""
+    _run("ogc_depth_points", depth, int(width), int(height), _view(view), _d(depth, "depth"), _i(face, "face"), _f(points, "points"),
+         _i(pixel, "pixel"), _i(face_out, "face_out"), _i(status, "status"))
+
+
 def png_unfilter(stream_bytes, height, row_bytes, bpp):
     """The row filters of an inflated PNG stream undone on the host (ogc_png_unfilter; nothing is launched): bytes of
     height * (1 + row_bytes) -> numpy uint8 (height, row_bytes)."""
