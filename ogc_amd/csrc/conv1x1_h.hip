@@ -253,12 +253,7 @@ __global__ __launch_bounds__(H_WAVES *OGC_WAVE, OCC) void conv1x1_gemm16_kernel(
                         const uint2 u = yv[a * 4 + r];
                         const float4 y = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
                                                      __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u));
-                        if (pro_relu) {
-                            o.x = fmaf(fa, y.x, fb) > 0.f ? o.x : 0.f; o.y = fmaf(fa, y.y, fb) > 0.f ? o.y : 0.f;
-                            o.z = fmaf(fa, y.z, fb) > 0.f ? o.z : 0.f; o.w = fmaf(fa, y.w, fb) > 0.f ? o.w : 0.f;
-                        }
-                        o.x = fmaf(al, o.x, fmaf(c2, y.x, c3)); o.y = fmaf(al, o.y, fmaf(c2, y.y, c3));
-                        o.z = fmaf(al, o.z, fmaf(c2, y.z, c3)); o.w = fmaf(al, o.w, fmaf(c2, y.w, c3));
+                        ogc_gn_adjoint(o, y, fa, fb, al, c2, c3, pro_relu);
                     }
                     if (mu + kk * 4 < M)                 // a wave-uniform base + ONE 32-bit lane offset (see load_tile)
                         ogc_st4(outb + (size_t)mu * hw + soff, o);

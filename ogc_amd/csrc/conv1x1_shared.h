@@ -55,6 +55,19 @@ __device__ __forceinline__ void ogc_affine_act(float4 &v, float a, float b, int 
     if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
 }
 
+// The GroupNorm adjoint on four consecutive positions of one row (gn_fused_bwd.hip): g, the input gradient W^T g_y, becomes
+//     alpha mask g + c2 y + c3,      mask = [fa y + fb > 0] (relu) or all ones
+// — the epilogue of dgrad_adjoint_kernel and of the adjoint form of conv1x1_gemm16_kernel (conv1x1_h.hip), which have to agree
+// bit for bit: the 16-bit entry point sends a shape to either.
+__device__ __forceinline__ void ogc_gn_adjoint(float4 &g, const float4 &y, float fa, float fb, float al, float c2, float c3, int relu) {
+    if (relu) {
+        g.x = fmaf(fa, y.x, fb) > 0.f ? g.x : 0.f; g.y = fmaf(fa, y.y, fb) > 0.f ? g.y : 0.f;
+        g.z = fmaf(fa, y.z, fb) > 0.f ? g.z : 0.f; g.w = fmaf(fa, y.w, fb) > 0.f ? g.w : 0.f;
+    }
+    g.x = fmaf(al, g.x, fmaf(c2, y.x, c3)); g.y = fmaf(al, g.y, fmaf(c2, y.y, c3));
+    g.z = fmaf(al, g.z, fmaf(c2, y.z, c3)); g.w = fmaf(al, g.w, fmaf(c2, y.w, c3));
+}
+
 __device__ __forceinline__ v4s ogc_pack_bf16(float a, float b, float c, float d) {
     typedef float v2f __attribute__((ext_vector_type(2)));
     typedef __bf16 v2bf __attribute__((ext_vector_type(2)));

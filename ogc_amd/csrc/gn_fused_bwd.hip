@@ -24,115 +24,10 @@
 #include "conv1x1_shared.h" // v4f, WG_WAVES, ogc_pooled_grad, the operand precision switch ogc_g_matmul_bf16 (conv1x1.hip)
 #include "act_io.h"
 #include "first_conv.h"
-#include "live_steps.h"
+#include "live_steps.h" // LiveIn, live_check (the lists are made in live_steps.hip)
+#include <type_traits>
 
 namespace {
-
-// ---- live steps: the 16-position steps of a level's neighbourhoods that hold more than repeats of column 0 ------------------------
-// (the rule, the packing of both lists, LiveIn and live_check: live_steps.h, shared with the forward list forms of conv1x1.hip)
-
-// One workgroup per sample.  Count: a wavefront reads 64 consecutive entries (64 / S whole rows) per load and finds each row's last
-// column that differs from column 0 with a ballot; the centre's live-step count goes to LDS.  Then a run of consecutive centres
-// per thread: sum, scan (as rev_scan_kernel of neighbour_loss.hip), write.
-// FWD: the forward list as well (live_steps.h; p * s is a multiple of 64).  The greedy pack is a walk over the groups with one
-// state, the slots u = 0 .. 3 used in the current tile; a run of groups maps u to the slots it consumes from there, pads included
-// (the state after it is (u + that) & 3), and such maps compose — a thread forms the map of its run of consecutive groups, the
-// same scan composes them, and the thread writes its run from the offset the runs in front of it consume from state 0.
-constexpr int LIVE_MAX_P = 32768; // centres per sample (one byte of LDS each)
-template <bool FWD>
-__global__ __launch_bounds__(1024) void live_steps_kernel(int p, int s, const int *__restrict__ idx, int *__restrict__ steps,
-                                                          int *__restrict__ n_live, int *__restrict__ fwd = nullptr,
-                                                          int *__restrict__ n_fwd = nullptr) {
-    __shared__ int part[1024];
-    __shared__ int fmap[FWD ? 4 * 1024 : 4]; // FWD: [u][thread] slots consumed from state u
-    __shared__ unsigned char cnt[LIVE_MAX_P];
-    const int t = threadIdx.x, b = blockIdx.x, T = s >> 4;
-    const int lane = t & 63, wave = t >> 6;
-    const int *ib = idx + (size_t)b * p * s;
-    int *out = steps + (size_t)b * p * T;
-    const int row0 = lane & ~(s - 1); // the lane of column 0 of this lane's row
-    const unsigned long long row_mask = (s == 64 ? ~0ull : (1ull << s) - 1ull) << row0;
-    const int total = p * s;          // (< 2^31: p <= LIVE_MAX_P, s <= 64)
-    for (int e0 = wave * 64; e0 < total; e0 += 1024) { // (wave-uniform trips; total is a multiple of s, so rows are whole)
-        const bool in = e0 + lane < total;
-        const int v = in ? ib[e0 + lane] : 0;
-        const int first = __shfl(v, row0);
-        const unsigned long long differs = __builtin_amdgcn_ballot_w64(in && v != first) & row_mask;
-        const int hi = differs ? 63 - __clzll(differs) - row0 : 0; // the last column that differs from column 0 (0: none)
-        if (in && lane == row0) cnt[(e0 + lane) / s] = (unsigned char)(min((hi + 1) >> 4, T - 1) + 1); // s* + 1
-    }
-    __syncthreads();
-    const int per = (p + 1023) / 1024;
-    const int c0 = min(t * per, p), c1 = min(c0 + per, p);
-    int sum = 0;
-    for (int c = c0; c < c1; ++c) sum += cnt[c];
-    part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int at = t > 0 ? part[t - 1] : 0;
-    for (int c = c0; c < c1; ++c) {
-        const int sl = cnt[c] - 1;
-        for (int st = 0; st <= sl; ++st) out[at++] = (c * T + st) | (st == sl ? (T - 1 - sl) << LIVE_SHIFT : 0);
-    }
-    if (t == 1023) n_live[b] = part[1023];
-    if constexpr (FWD) {
-        const int cpg = 4 / T;                 // centres per group: 1 (s = 64) or 2 (s = 32)
-        const int groups = p / cpg;            // (p * T is a multiple of 4)
-        const int gper = (groups + 1023) / 1024;
-        const int g0 = min(t * gper, groups), g1 = min(g0 + gper, groups);
-        auto group_size = [&](int g) { return cpg == 1 ? (int)cnt[g] : (int)cnt[2 * g] + (int)cnt[2 * g + 1]; };
-        int len[4] = {0, 0, 0, 0};
-        for (int g = g0; g < g1; ++g) {
-            const int sz = group_size(g);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int used = (u + len[u]) & 3;
-                len[u] += (used + sz > 4 ? 4 - used : 0) + sz;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) fmap[u * 1024 + t] = len[u];
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) { // inclusive scan: the runs t - off + 1 .. t, composed left to right
-            int left[4] = {0, 0, 0, 0};
-            if (t >= off) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) left[u] = fmap[u * 1024 + t - off];
-            }
-            __syncthreads();
-            if (t >= off) {
-                int mine[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) mine[u] = fmap[((u + left[u]) & 3) * 1024 + t];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) left[u] += mine[u];
-            }
-            __syncthreads();
-            if (t >= off) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) fmap[u * 1024 + t] = left[u];
-            }
-            __syncthreads();
-        }
-        int *fo = fwd + (size_t)b * p * T;
-        int fat = t > 0 ? fmap[t - 1] : 0; // from state 0
-        for (int g = g0; g < g1; ++g) {
-            const int used = fat & 3;
-            if (used + group_size(g) > 4)
-                for (int u = used; u < 4; ++u) fo[fat++] = LIVE_PAD;
-            for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
-                const int sl = cnt[c] - 1;
-                for (int st = 0; st <= sl; ++st) fo[fat++] = (c * T + st) | (st == sl ? (T - 1 - sl) << LIVE_SHIFT : 0);
-            }
-        }
-        if (t == 1023) n_fwd[b] = fmap[1023];
-    }
-}
 
 // ---- moment matrices ------------------------------------------------------------------------------------------------
 // Same operand layout as conv1x1_wgrad_kernel: for a step of 16 positions lane (i = l & 15, k = l >> 4) loads ONE float4 =
@@ -144,9 +39,22 @@ __global__ __launch_bounds__(1024) void live_steps_kernel(int p, int s, const in
 // AT: element type of x and dy (float / ogc_bf16: act_io.h).
 // FIRST (0: off, else the CP of first_conv.h): x is the output of a first convolution that was never stored; a lane rebuilds its
 // CIB float4 of it from the x0 values at its four positions (loaded in x's place) and the rows of W1 it holds in registers.
-// LIST: the wave walks entries of the sample's live-step list (LiveIn above) instead of consecutive steps, its share derived
+// LIST: the wave walks entries of the sample's live-step list (LiveIn: live_steps.h) instead of consecutive steps, its share derived
 // from the list's length so that the live steps spread over all workgroups of the sample; the g_y operand of an entry's last
 // position is multiplied by the entry's weight (the skipped repeats of that column).
+// The body both moment kernels share is moments_body.inc + moments_walk.inc.  What they differ in: the STEP — positions per step
+// (1 << SHIFT) and per lane (PER), what a lane loads, where its positions lie inside a neighbourhood — and `fma`, the transform
+// from the loaded dy / x to the MFMA operands with the products into acc1 (H) and acc2 (H2), which each kernel spells itself.
+struct MomentStep16 { // fp32 tensors, 16 positions per step
+    static constexpr int SHIFT = 4, PER = 4;
+    typedef float4 Raw;
+    template <typename T>
+    static __device__ inline void ld(const T *p, Raw &r) { r = ogc_ld4(p); }
+    // (the step lies inside one neighbourhood: pb is a multiple of 16)
+    static __device__ inline int centre(int pb, int k, int s_shift) { return pb >> s_shift; }
+    static __device__ inline int inside(int pb, int k, int smask) { return (pb & smask) + 4 * k; }
+};
+
 template <int COB, int CIB, bool POOLED, typename AT = float, int FIRST = 0, bool LIST = false>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int cin, int cout, int hw, int chunks,
                                                                            int steps_per_wave, int relu,
@@ -159,89 +67,10 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
                                                                            int s_shift,
                                                                            float *__restrict__ hm,        // (B, 2, cout, cin)
                                                                            FirstIn first = FirstIn(), LiveIn ls = LiveIn()) {
-    constexpr int XN = FIRST ? FIRST : CIB; // float4 a lane loads per step in x's place
-    __shared__ float red[WG_WAVES][COB * CIB * 256]; // one slab per wave (see conv1x1_wgrad_kernel), H then H2
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i = lane & 15, k = lane >> 4;
-    const int img = blockIdx.x / chunks, chunk = blockIdx.x - img * chunks;
-    const int co0 = blockIdx.y * (16 * COB), ci0 = blockIdx.z * (16 * CIB);
-    int steps_per_img = hw >> 4;
-    const int *lv_ = nullptr;
-    if constexpr (LIST) {
-        steps_per_img = min(ls.n[img], ls.cap); // entries of the list (>= 1: every centre keeps its first step)
-        lv_ = ls.steps + (size_t)img * ls.cap;
-        const int waves = chunks * WG_WAVES;
-        steps_per_wave = ((steps_per_img + waves - 1) / waves + 1) & ~1;
-        if (chunk * WG_WAVES * steps_per_wave >= steps_per_img) return; // (the whole workgroup, ahead of every barrier)
-    }
-    const int first_step = (chunk * WG_WAVES + wave) * steps_per_wave;
-    const int mine = max(0, min(steps_per_wave, steps_per_img - first_step)); // this wavefront's steps: [first_step, first_step + mine)
-
-    v4f acc1[COB][CIB], acc2[COB][CIB];
-#pragma unroll
-    for (int a = 0; a < COB; ++a)
-#pragma unroll
-        for (int c = 0; c < CIB; ++c) {
-            acc1[a][c] = (v4f){0.f, 0.f, 0.f, 0.f};
-            acc2[a][c] = (v4f){0.f, 0.f, 0.f, 0.f};
-        }
-    int yrow[COB], xrow[XN], jrow[COB];
-    float ca[CIB], cb[CIB], pc2[COB], pc3[COB];
-    float w1r[FIRST ? CIB : 1][FIRST ? FIRST : 1]; // FIRST: the rows of W1 of this lane's CIB channels (zeros beyond c0)
-    const int centres = hw >> s_shift, smask = (1 << s_shift) - 1;
-#pragma unroll
-    for (int a = 0; a < COB; ++a) {
-        const int row = min(co0 + a * 16 + i, cout - 1);
-        yrow[a] = row * hw;
-        if (POOLED) {
-            const float2 cc = coef2[(size_t)img * cout + row];
-            pc2[a] = cc.x;
-            pc3[a] = cc.y;
-            jrow[a] = row * centres;
-        }
-    }
-    const float2 *jb_ = POOLED ? inj + (size_t)img * cout * centres : nullptr;
-#pragma unroll
-    for (int c = 0; c < CIB; ++c) {
-        const int ch = min(ci0 + c * 16 + i, cin - 1);
-        if constexpr (FIRST == 0) xrow[c] = ch * hw;
-        ca[c] = aff_a[(size_t)img * cin + ch];
-        cb[c] = aff_b[(size_t)img * cin + ch];
-        if constexpr (FIRST > 0) {
-#pragma unroll
-            for (int e = 0; e < FIRST; ++e) w1r[c][e] = e < first.c0 ? first.w1[ch * first.c0 + min(e, first.c0 - 1)] : 0.f;
-        }
-    }
-    if constexpr (FIRST > 0) { // one load shape per channel of x0; channels beyond c0 re-read the last one and are zeroed in fma16
-#pragma unroll
-        for (int e = 0; e < FIRST; ++e) xrow[e] = min(e, first.c0 - 1) * hw;
-    }
-    const AT *yb_ = dy + (size_t)img * cout * hw + 4 * k;
-    const AT *xb_ = FIRST ? reinterpret_cast<const AT *>(first.x0) + (size_t)img * first.c0 * hw + 4 * k
-                          : x + (size_t)img * cin * hw + 4 * k;
-    int cur = min(first_step, steps_per_img - 1);
-    const int stop = min(first_step + mine, steps_per_img) - 1; // the walk stays on the wave's last step once it is reached
-    // Unconditional loads of one shape (see conv1x1_wgrad_kernel: a load under a per-lane condition makes the compiler wait
-    // for ALL outstanding loads wherever it needs one, which serialises the ping-pong): rows beyond the tensors are clamped
-    // onto the last row — they only reach rows / columns of H, H2 that are never stored — and steps beyond the wave's
-    // share re-read its last step and are not computed with.
-    int ent = LIST ? lv_[cur] : 0; // LIST: the entry of step `cur` (wave-uniform), fetched one step ahead of its loads
-    auto load = [&](float4(&yv)[COB], float4(&xv)[XN], float2(&jv)[COB], int &jpos, int &went) { // step `cur`, then advance
-        const int pb = LIST ? min(ent & LIVE_MASK, (hw >> 4) - 1) * 16 : cur * 16;
-        if constexpr (LIST) went = ent; // (wave-uniform: the weight is formed where it is used)
-#pragma unroll
-        for (int a = 0; a < COB; ++a) yv[a] = ogc_ld4(yb_ + yrow[a] + pb);
-#pragma unroll
-        for (int c = 0; c < XN; ++c) xv[c] = ogc_ld4(xb_ + xrow[c] + pb);
-        if (POOLED) {
-#pragma unroll
-            for (int a = 0; a < COB; ++a) jv[a] = jb_[jrow[a] + (pb >> s_shift)];
-            jpos = (pb & smask) + 4 * k; // this lane's first position inside the neighbourhood
-        }
-        cur = min(cur + 1, max(stop, 0));
-        if constexpr (LIST) ent = lv_[cur];
-    };
-    auto fma16 = [&](float4(&yv)[COB], const float4(&xraw)[XN], const float2(&jv)[COB], int jpos, int went) {
+    typedef MomentStep16 STEP;
+#include "moments_body.inc"
+    // the transform: g_y rebuilt (POOLED) and weighted (LIST), x rebuilt (FIRST), then the mask and mask . x as fp32 operands
+    auto fma = [&](float4(&yv)[COB], const float4(&xraw)[XN], const float2(&jv)[COB], int jpos, int went) {
         if (POOLED) {
 #pragma unroll
             for (int a = 0; a < COB; ++a) ogc_pooled_grad(yv[a], pc2[a], pc3[a], jv[a], jpos); // (gn_maxpool_bwd_dx_kernel's expression)
@@ -285,40 +114,7 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
                 acc2[a][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[a].w, m2[c].w, acc2[a][c], 0, 0, 0);
             }
     };
-
-    float4 ya[COB], xa[XN], yb[COB], xb[XN];
-    float2 ja[COB], jb[COB];
-    int pa_ = 0, pb_ = 0;
-    int wa_ = 0, wb_ = 0;
-    load(ya, xa, ja, pa_, wa_);
-    int s = 0;
-    for (; s + 1 < mine; s += 2) { // ping-pong registers: next step's loads fly during the MFMAs (no branch in the body)
-        load(yb, xb, jb, pb_, wb_);
-        fma16(ya, xa, ja, pa_, wa_);
-        load(ya, xa, ja, pa_, wa_);
-        fma16(yb, xb, jb, pb_, wb_);
-    }
-    if (s < mine) fma16(ya, xa, ja, pa_, wa_);
-
-    float *dst = hm + (size_t)img * 2 * cout * cin;
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-        if (which) __syncthreads();
-#pragma unroll
-        for (int a = 0; a < COB; ++a)
-#pragma unroll
-            for (int c = 0; c < CIB; ++c)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) // C/D layout: lane l holds rows (l >> 4) * 4 + r of column l & 15
-                    red[wave][(a * CIB + c) * 256 + (k * 4 + r) * 16 + i] = which ? acc2[a][c][r] : acc1[a][c][r];
-        __syncthreads();
-        for (int t = threadIdx.x; t < COB * CIB * 256; t += WG_WAVES * OGC_WAVE) {
-            const int blk = t >> 8, a = blk / CIB, c = blk % CIB;
-            const int row = co0 + a * 16 + ((t & 255) >> 4), col = ci0 + c * 16 + (t & 15);
-            const float v = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-            if (row < cout && col < cin && v != 0.0f) unsafeAtomicAdd(dst + ((size_t)which * cout + row) * cin + col, v);
-        }
-    }
+#include "moments_walk.inc"
 }
 
 // ---- the moment matrices from 16-bit tensors --------------------------------------------------------------------------------
@@ -331,6 +127,15 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments_kernel(int c
 // POOLED form rebuilds g_y in fp32 and rounds it (bf16 operands, as everywhere under ogc_set_matmul_precision(1)).
 typedef short v4s16 __attribute__((ext_vector_type(4)));
 
+struct MomentStep32 { // bf16 tensors, 32 positions per step
+    static constexpr int SHIFT = 5, PER = 8;
+    typedef uint4 Raw;
+    static __device__ inline void ld(const ogc_bf16 *p, Raw &r) { r = *reinterpret_cast<const uint4 *>(p); }
+    // (a lane's eight positions lie inside one neighbourhood, the step's 32 need not: S >= 16)
+    static __device__ inline int centre(int pb, int k, int s_shift) { return (pb + 8 * k) >> s_shift; }
+    static __device__ inline int inside(int pb, int k, int smask) { return (pb + 8 * k) & smask; }
+};
+
 template <int COB, int CIB, bool POOLED>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments16_kernel(int cin, int cout, int hw, int chunks,
                                                                              int steps_per_wave, int relu,
@@ -342,64 +147,18 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments16_kernel(int
                                                                              const float2 *__restrict__ inj,   // (B, cout, hw >> s_shift)
                                                                              int s_shift,
                                                                              float *__restrict__ hm) {         // (B, 2, cout, cin)
-    __shared__ float red[WG_WAVES][COB * CIB * 256];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i = lane & 15, k = lane >> 4;
-    const int img = blockIdx.x / chunks, chunk = blockIdx.x - img * chunks;
-    const int co0 = blockIdx.y * (16 * COB), ci0 = blockIdx.z * (16 * CIB);
-    const int steps_per_img = hw >> 5;
-    const int first = (chunk * WG_WAVES + wave) * steps_per_wave;
-    const int mine = max(0, min(steps_per_wave, steps_per_img - first));
-
-    v4f acc1[COB][CIB], acc2[COB][CIB];
-#pragma unroll
-    for (int a = 0; a < COB; ++a)
-#pragma unroll
-        for (int c = 0; c < CIB; ++c) {
-            acc1[a][c] = (v4f){0.f, 0.f, 0.f, 0.f};
-            acc2[a][c] = (v4f){0.f, 0.f, 0.f, 0.f};
-        }
-    int yrow[COB], xrow[CIB], jrow[COB];
-    float ca[CIB], cb[CIB], pc2[COB], pc3[COB];
-    const int centres = hw >> s_shift, smask = (1 << s_shift) - 1;
-#pragma unroll
-    for (int a = 0; a < COB; ++a) {
-        const int row = min(co0 + a * 16 + i, cout - 1);
-        yrow[a] = row * hw;
-        if (POOLED) {
-            const float2 cc = coef2[(size_t)img * cout + row];
-            pc2[a] = cc.x;
-            pc3[a] = cc.y;
-            jrow[a] = row * centres;
-        }
-    }
-    const float2 *jb_ = POOLED ? inj + (size_t)img * cout * centres : nullptr;
-#pragma unroll
-    for (int c = 0; c < CIB; ++c) {
-        const int ch = min(ci0 + c * 16 + i, cin - 1);
-        xrow[c] = ch * hw;
-        ca[c] = aff_a[(size_t)img * cin + ch];
-        cb[c] = aff_b[(size_t)img * cin + ch];
-    }
-    const ogc_bf16 *yb_ = dy + (size_t)img * cout * hw + 8 * k;
-    const ogc_bf16 *xb_ = x + (size_t)img * cin * hw + 8 * k;
-    int cur = min(first, steps_per_img - 1);
-    const int stop = min(first + mine, steps_per_img) - 1;
-    // (unconditional loads of one shape, clamped rows and steps: see wgrad_moments_kernel)
-    auto load = [&](uint4(&yv)[COB], uint4(&xv)[CIB], float2(&jv)[COB], int &jpos) { // step `cur`, then advance
-        const int pb = cur * 32;
-#pragma unroll
-        for (int a = 0; a < COB; ++a) yv[a] = *reinterpret_cast<const uint4 *>(yb_ + yrow[a] + pb);
-#pragma unroll
-        for (int c = 0; c < CIB; ++c) xv[c] = *reinterpret_cast<const uint4 *>(xb_ + xrow[c] + pb);
-        if (POOLED) { // a lane's eight positions lie inside one neighbourhood (S >= 16)
-#pragma unroll
-            for (int a = 0; a < COB; ++a) jv[a] = jb_[jrow[a] + ((pb + 8 * k) >> s_shift)];
-            jpos = (pb + 8 * k) & smask;
-        }
-        cur = min(cur + 1, max(stop, 0));
-    };
-    auto fma32 = [&](const uint4(&yraw)[COB], const uint4(&xraw)[CIB], const float2(&jv)[COB], int jpos) {
+    // What the body asks for by name and this kernel does not take: the first-layer and list forms exist for fp32 tensors only
+    // (a step of 32 positions fits neither the x0 rebuild nor the 16-position entries of a list).
+    typedef ogc_bf16 AT;
+    constexpr int FIRST = 0;
+    constexpr bool LIST = false;
+    static_assert(FIRST == 0 && !LIST, "wgrad_moments16_kernel: no first-layer form and no list form");
+    const FirstIn first = FirstIn();
+    const LiveIn ls = LiveIn();
+    typedef MomentStep32 STEP;
+#include "moments_body.inc"
+    // the transform: dy as loaded (POOLED: rebuilt in fp32 and rounded), the mask and mask . x as bit masks on the packed x
+    auto fma = [&](const uint4(&yraw)[COB], const uint4(&xraw)[CIB], const float2(&jv)[COB], int jpos, int) {
         v4s16 y0[COB], y1[COB];
 #pragma unroll
         for (int a = 0; a < COB; ++a) {
@@ -441,46 +200,14 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void wgrad_moments16_kernel(int
                 acc2[a][c] = ogc_mfma_bf16_k32(y0[a], y1[a], m2a[c], m2b[c], acc2[a][c]);
             }
     };
-
-    uint4 ya[COB], xa[CIB], yb[COB], xb[CIB];
-    float2 ja[COB], jb[COB];
-    int pa_ = 0, pb_ = 0;
-    load(ya, xa, ja, pa_);
-    int s = 0;
-    for (; s + 1 < mine; s += 2) { // ping-pong registers: next step's loads fly during the MFMAs (no branch in the body)
-        load(yb, xb, jb, pb_);
-        fma32(ya, xa, ja, pa_);
-        load(ya, xa, ja, pa_);
-        fma32(yb, xb, jb, pb_);
-    }
-    if (s < mine) fma32(ya, xa, ja, pa_);
-
-    float *dst = hm + (size_t)img * 2 * cout * cin;
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-        if (which) __syncthreads();
-#pragma unroll
-        for (int a = 0; a < COB; ++a)
-#pragma unroll
-            for (int c = 0; c < CIB; ++c)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    red[wave][(a * CIB + c) * 256 + (k * 4 + r) * 16 + i] = which ? acc2[a][c][r] : acc1[a][c][r];
-        __syncthreads();
-        for (int t = threadIdx.x; t < COB * CIB * 256; t += WG_WAVES * OGC_WAVE) {
-            const int blk = t >> 8, a = blk / CIB, c = blk % CIB;
-            const int row = co0 + a * 16 + ((t & 255) >> 4), col = ci0 + c * 16 + (t & 15);
-            const float v = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-            if (row < cout && col < cin && v != 0.0f) unsafeAtomicAdd(dst + ((size_t)which * cout + row) * cin + col, v);
-        }
-    }
+#include "moments_walk.inc"
 }
 
-
-template <int COB, int CIB, typename AT, int FIRST = 0>
+// One tile of the ladder below: the launch geometry, then the kernel — the list form wherever a list came along (fp32 only).
+template <int COB, int CIB, typename AT, int FIRST, bool POOLED>
 void moments_launch(int b, int cin, int cout, int hw, int relu, const AT *x, const AT *dy, const float *pa,
                     const float *pb, const float *coef2, const float *inj, int s_shift, float *hm, hipStream_t s,
-                    FirstIn first = FirstIn(), LiveIn ls = LiveIn()) {
+                    const FirstIn &first, const LiveIn &ls) {
     const int steps_per_img = sizeof(AT) == 2 ? hw >> 5 : hw >> 4; // (16-bit tensors: 32 positions per step)
     const int tiles = ogc_divup(cout, 16 * COB) * ogc_divup(cin, 16 * CIB);
     long long waves = (2048 / tiles) / b;            // wavefronts per sample and tile pair: ~2048 over the chip
@@ -491,34 +218,51 @@ void moments_launch(int b, int cin, int cout, int hw, int relu, const AT *x, con
     const int chunks = ogc_divup(steps_per_img, spw * WG_WAVES);
     dim3 grid(b * chunks, ogc_divup(cout, 16 * COB), ogc_divup(cin, 16 * CIB));
     const float2 *c2 = reinterpret_cast<const float2 *>(coef2), *ij = reinterpret_cast<const float2 *>(inj);
-    if constexpr (sizeof(AT) == 2) {
-        if (inj)
-            hipLaunchKernelGGL((wgrad_moments16_kernel<COB, CIB, true>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
-                               chunks, spw, relu, x, dy, pa, pb, c2, ij, s_shift, hm);
-        else
-            hipLaunchKernelGGL((wgrad_moments16_kernel<COB, CIB, false>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
-                               chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm);
-    } else if constexpr (FIRST > 0) {
-        if (ls.steps) // (grid of the worst case: every step live; the kernel derives its share from the list's length)
-            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT, FIRST, true>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout,
-                               hw, chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm, first, ls);
-        else
-            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT, FIRST>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
-                               chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm, first, ls);
-    } else {
-        if (inj && ls.steps)
-            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, true, AT, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
-                               chunks, spw, relu, x, dy, pa, pb, c2, ij, s_shift, hm, first, ls);
-        else if (inj)
-            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, true, AT>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw, chunks,
-                               spw, relu, x, dy, pa, pb, c2, ij, s_shift, hm);
-        else if (ls.steps) // (the plain list form: a middle layer behind a pooled tail that wrote dy at live positions only)
-            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw,
-                               chunks, spw, relu, x, dy, pa, pb, c2, ij, 0, hm, first, ls);
-        else
-            hipLaunchKernelGGL((wgrad_moments_kernel<COB, CIB, false, AT>), grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw, chunks,
-                               spw, relu, x, dy, pa, pb, c2, ij, 0, hm);
+    auto go = [&](auto kernel, auto... tail) {
+        hipLaunchKernelGGL(kernel, grid, dim3(WG_WAVES * OGC_WAVE), 0, s, cin, cout, hw, chunks, spw, relu, x, dy, pa, pb, c2, ij,
+                           s_shift, hm, tail...);
+    };
+    if constexpr (sizeof(AT) == 2) go(wgrad_moments16_kernel<COB, CIB, POOLED>);
+    else if (ls.steps) // (grid of the worst case: every step live; the kernel derives its share from the list's length)
+        go(wgrad_moments_kernel<COB, CIB, POOLED, AT, FIRST, true>, first, ls);
+    else go(wgrad_moments_kernel<COB, CIB, POOLED, AT, FIRST>, first, ls);
+}
+
+// The tile ladder: (COB, CIB) row and column blocks of 16 per workgroup, by the channel counts; launch(COB, CIB) takes them as
+// integral constants.  MAXC: column blocks at most — 2 for the first-layer forms, where beyond 32 channels of y1 the grid's z
+// dimension walks the column tiles (the recomputed operand costs registers the <.., 4> forms do not have).  WIDE: the widest
+// tile is <4, 4>; without it <4, 2> — the pooled fp32 <4, 4> runs out of registers (256 + 34) and is not compiled.
+template <int N>
+using TileC = std::integral_constant<int, N>;
+template <int MAXC, bool WIDE, typename F>
+void moments_ladder(int cin, int cout, F launch) {
+    if (cout <= 16 && cin <= 16) launch(TileC<1>(), TileC<1>());
+    else if (cout <= 32 && cin <= 16) launch(TileC<2>(), TileC<1>());
+    else if (cout <= 32 && (cin <= 32 || MAXC == 2)) launch(TileC<2>(), TileC<2>());
+    else if (cin <= 16) launch(TileC<4>(), TileC<1>());
+    else if (cin <= 32 || MAXC == 2) launch(TileC<4>(), TileC<2>());
+    else if constexpr (MAXC == 4) {
+        if (cout <= 32) launch(TileC<2>(), TileC<4>());
+        else if constexpr (WIDE) launch(TileC<4>(), TileC<4>());
+        else launch(TileC<4>(), TileC<2>());
     }
+}
+
+// What every moment entry point ends in, its own checks done: H, H2 zeroed (the kernels add into them), the ladder, the launch.
+template <typename AT, int FIRST, bool POOLED>
+int moments_run(const char *name, int b, int cin, int cout, int hw, int relu, const AT *x, const AT *dy, const float *pa,
+                const float *pb, const float *coef2, const float *inj, int s_shift, float *moments, hipStream_t s,
+                const FirstIn &first, const LiveIn &ls) {
+    if (ogc_zero_async(moments, sizeof(float) * 2 * (size_t)b * cin * cout, s) != hipSuccess) {
+        ogc_set_error("%s: memset failed", name);
+        return OGC_ERR_LAUNCH;
+    }
+    moments_ladder<FIRST ? 2 : 4, !(POOLED && sizeof(AT) == 4)>(cin, cout, [&](auto cob, auto cib) {
+        moments_launch<decltype(cob)::value, decltype(cib)::value, AT, FIRST, POOLED>(b, cin, cout, hw, relu, x, dy, pa, pb, coef2, inj,
+                                                                                     s_shift, moments, s, first, ls);
+    });
+    OGC_CHECK_LAUNCH(name);
+    return OGC_OK;
 }
 
 // ---- dW, the GroupNorm parameter gradients and the coefficients of the adjoint ----------------------------------------------
@@ -608,7 +352,7 @@ __global__ __launch_bounds__(256) void moments_combine_kernel(int b, int cin, in
 // the weight gradient of that convolution, dW1[m][c] = sum_p g_prev[m][p] x0[c][p], which the epilogue forms from the four
 // positions it holds: summed over the 16 lanes of a DPP row, then over the workgroup's run of first.run position tiles in LDS,
 // then one fp32 atomic per element and workgroup into first.dw1.
-// LIST (fp32): a wave's tile is FOUR ENTRIES of the sample's live-step list (LiveIn above) instead of 64
+// LIST (fp32): a wave's tile is FOUR ENTRIES of the sample's live-step list (LiveIn: live_steps.h) instead of 64
 // consecutive positions — lane j holds positions 4 (j & 3) .. + 3 of entry 4 tile + (j >> 2); the geometry of S = 16, four
 // neighbourhoods per tile, and the pooled table is sized for it (its per-row pair (c2, c3) apart from the per-entry pair (ag, arg):
 // at K = 128 the weight tile and a table of whole float4 would not fit 64 KiB).  POOLED writes g_prev at live positions only; FIRST
@@ -616,6 +360,24 @@ __global__ __launch_bounds__(256) void moments_combine_kernel(int b, int cin, in
 // length.  Neither (the plain form, a middle layer between a pooled tail and a layer that reads its gradient densely) reads g_y and
 // y_prev at live positions only and writes g_prev DENSELY: the steps an entry skips (s_shift: log2 of the neighbourhood size,
 // which bounds them) repeat the entry's last position bit for bit, so the four lanes that hold the entry store that value there.
+// The pooled forms' table: (c2, c3, ag, arg) of the wave's K rows x (64 >> s_shift) neighbourhoods through wave-private LDS, read
+// back one entry per row right where it is used (held in registers next to the K x 64 tile they cost a wavefront per SIMD).
+// Dense: one float4 per row and neighbourhood (cpw columns per row).  LIST: one column per entry of the tile, (ag, arg) per row
+// and entry in tabj, then (c2, c3) per row in tabc — 40 bytes per row and wave instead of 64.
+// This is the read-back, (c2, c3, ag, arg) of `row` in the lane's neighbourhood (LIST: entry) `mine` of the tile.  The fill is
+// text in the kernel: as a function next to this one — five shapes of it: with the table as a struct or as pointers, scalars by
+// value or by reference, always_inline or not — it moved the spilled SGPRs of dgrad_adjoint_kernel<33 / 40, true, bf16, true>
+// (8 -> 16 and 30 -> 28; <8 / 16 / 25, .., LIST> by one SGPR in the first shape), and with the kernel's own text they stay.
+template <bool LIST>
+__device__ inline float4 pooled_table_row(const float4 *tab, const float2 *tabj, const float2 *tabc, int cpw, int row, int mine) {
+    if constexpr (LIST) {
+        const float2 cc = tabc[row], jj = tabj[row * 4 + mine];
+        return make_float4(cc.x, cc.y, jj.x, jj.y);
+    } else {
+        return tab[row * cpw + mine];
+    }
+}
+
 template <int KQ, bool POOLED, typename AT = float, bool BF = false, int FIRST = 0, bool LIST = false>
 __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M, int K, int hw, int relu,
                                                                            const float *__restrict__ w,     // (K, M)
@@ -658,213 +420,194 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
         for (int t = threadIdx.x; t < FC_MAX_ROWS * FC_MAX_C0; t += WG_WAVES * OGC_WAVE) s_dw[t] = 0.f;
     }
     for (int it = 0; it < run; ++it) {
-    const int tw = (blockIdx.x * run + it) * WG_WAVES + wave; // the wave's tile
-    const int p0 = tw * 64;
-    const bool live = LIST ? 4 * tw < n_lv : p0 < hw;
-    int pos = p0 + 4 * j; // the lane's first position
-    bool mine_ok = true;  // LIST: the lane's entry exists (the last tile of a list may hold fewer than four)
-    float wl = 1.f;       // LIST: the weight of the lane's LAST position (.w)
-    int skipped = 0;      // LIST, plain form: the steps behind the lane's entry that repeat its last position
-    if constexpr (LIST) {
-        const int q = 4 * tw + (j >> 2);
-        mine_ok = q < n_lv;
-        const int ent = lv_[min(q, n_lv - 1)];
-        const int step = min(ent & LIVE_MASK, (hw >> 4) - 1);
-        pos = step * 16 + 4 * (j & 3);
-        wl = (j & 3) == 3 ? (float)(1 + 16 * (ent >> LIVE_SHIFT)) : 1.f;
-        if constexpr (!POOLED && FIRST == 0) { // (clamped to the steps left in the centre, as the step is clamped to the sample)
-            const int tmask = (1 << (s_shift - 4)) - 1;
-            skipped = mine_ok ? min(max(ent >> LIVE_SHIFT, 0), tmask - (step & tmask)) : 0;
-        }
-    }
-    const bool lane_live = live && mine_ok;
-    float4 x0v[FIRST ? FIRST : 1];
-    if constexpr (FIRST > 0) {
-        ogc_first_load_raw<FIRST>(x0v, first.x0 + (size_t)b * first.c0 * hw + (live ? pos : 0), first.c0, hw);
-        ogc_first_mask<FIRST>(x0v, first.c0, lane_live);
-    }
-
-    float4 xin[KQ];
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        const int row = q * 4 + kk;
-        xin[q] = (lane_live && row < K) ? ogc_ld4(inb + (size_t)row * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if (POOLED) {
-        // (c2, c3, ag, arg) of the wave's K rows x (64 >> s_shift) neighbourhoods through a wave-private LDS table: read back one
-        // 16-byte entry per row right where it is used (held in registers next to the K x 64 tile they cost a wavefront per SIMD)
-        const int centres = hw >> s_shift, cpw = LIST ? 4 : 64 >> s_shift; // LIST: one table column per entry of the tile
-        float4 *tab = reinterpret_cast<float4 *>(cf + 64 * 5) + (size_t)wave * K * cpw;
-        // LIST: (ag, arg) per row and entry, then (c2, c3) per row — 40 bytes per row and wave instead of 64
-        float2 *tabj = reinterpret_cast<float2 *>(cf + 64 * 5) + (size_t)wave * K * 5, *tabc = tabj + K * 4;
+        const int tw = (blockIdx.x * run + it) * WG_WAVES + wave; // the wave's tile
+        const int p0 = tw * 64;
+        const bool live = LIST ? 4 * tw < n_lv : p0 < hw;
+        int pos = p0 + 4 * j; // the lane's first position
+        bool mine_ok = true;  // LIST: the lane's entry exists (the last tile of a list may hold fewer than four)
+        float wl = 1.f;       // LIST: the weight of the lane's LAST position (.w)
+        int skipped = 0;      // LIST, plain form: the steps behind the lane's entry that repeat its last position
         if constexpr (LIST) {
-            for (int e = lane; e < K; e += OGC_WAVE) tabc[e] = coef2[(size_t)b * K + e];
-        }
-        for (int e = lane; e < K * cpw; e += OGC_WAVE) {
-            const int row = e / cpw;
-            int centre = (p0 >> s_shift) + (e - row * cpw);
-            if constexpr (LIST) {
-                const int q = 4 * tw + (e - row * cpw);
-                const int step = min(lv_[min(q, n_lv - 1)] & LIVE_MASK, (hw >> 4) - 1);
-                centre = q < n_lv ? (step * 16) >> s_shift : centres;
+            const int q = 4 * tw + (j >> 2);
+            mine_ok = q < n_lv;
+            const int ent = lv_[min(q, n_lv - 1)];
+            const int step = min(ent & LIVE_MASK, (hw >> 4) - 1);
+            pos = step * 16 + 4 * (j & 3);
+            wl = (j & 3) == 3 ? (float)(1 + 16 * (ent >> LIVE_SHIFT)) : 1.f;
+            if constexpr (!POOLED && FIRST == 0) { // (clamped to the steps left in the centre, as the step is clamped to the sample)
+                const int tmask = (1 << (s_shift - 4)) - 1;
+                skipped = mine_ok ? min(max(ent >> LIVE_SHIFT, 0), tmask - (step & tmask)) : 0;
             }
-            const float2 cc = coef2[(size_t)b * K + row];
-            const float2 jj = (live && centre < centres) ? inj[((size_t)b * K + row) * centres + centre]
-                                                         : make_float2(0.f, __int_as_float(-1));
-            if constexpr (LIST) tabj[e] = jj;
-            else tab[e] = make_float4(cc.x, cc.y, jj.x, jj.y);
         }
-        __syncthreads();
-        const int mine = LIST ? j >> 2 : (4 * j) >> s_shift, jpos = pos & ((1 << s_shift) - 1);
+        const bool lane_live = live && mine_ok;
+        float4 x0v[FIRST ? FIRST : 1];
+        if constexpr (FIRST > 0) {
+            ogc_first_load_raw<FIRST>(x0v, first.x0 + (size_t)b * first.c0 * hw + (live ? pos : 0), first.c0, hw);
+            ogc_first_mask<FIRST>(x0v, first.c0, lane_live);
+        }
+
+        float4 xin[KQ];
 #pragma unroll
-        for (int q = 0; q < KQ; ++q) { // the expression of gn_maxpool_bwd_dx_kernel, bit for bit (rows beyond K stay zero)
+        for (int q = 0; q < KQ; ++q) {
             const int row = q * 4 + kk;
-            if (row < K) { // (implies q < Kq; one predicate per row keeps the masks of 33 rows out of spilled SGPRs)
-                float4 t;
+            xin[q] = (lane_live && row < K) ? ogc_ld4(inb + (size_t)row * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (POOLED) { // g_y rebuilt from y through the wave's table (pooled_table_row above)
+            const int centres = hw >> s_shift, cpw = LIST ? 4 : 64 >> s_shift; // LIST: one table column per entry of the tile
+            float4 *tab = reinterpret_cast<float4 *>(cf + 64 * 5) + (size_t)wave * K * cpw;
+            float2 *tabj = reinterpret_cast<float2 *>(cf + 64 * 5) + (size_t)wave * K * 5, *tabc = tabj + K * 4;
+            if constexpr (LIST) {
+                for (int e = lane; e < K; e += OGC_WAVE) tabc[e] = coef2[(size_t)b * K + e];
+            }
+            for (int e = lane; e < K * cpw; e += OGC_WAVE) {
+                const int row = e / cpw;
+                int centre = (p0 >> s_shift) + (e - row * cpw);
                 if constexpr (LIST) {
-                    const float2 cc = tabc[row], jj = tabj[row * 4 + mine];
-                    t = make_float4(cc.x, cc.y, jj.x, jj.y);
-                } else {
-                    t = tab[row * cpw + mine];
+                    const int q = 4 * tw + (e - row * cpw);
+                    const int step = min(lv_[min(q, n_lv - 1)] & LIVE_MASK, (hw >> 4) - 1);
+                    centre = q < n_lv ? (step * 16) >> s_shift : centres;
                 }
-                const int rel = __float_as_int(t.w) - jpos;
-                xin[q].x = fmaf(t.x, xin[q].x, t.y) + (rel == 0 ? t.z : 0.f);
-                xin[q].y = fmaf(t.x, xin[q].y, t.y) + (rel == 1 ? t.z : 0.f);
-                xin[q].z = fmaf(t.x, xin[q].z, t.y) + (rel == 2 ? t.z : 0.f);
-                xin[q].w = fmaf(t.x, xin[q].w, t.y) + (rel == 3 ? t.z : 0.f);
+                const float2 cc = coef2[(size_t)b * K + row];
+                const float2 jj = (live && centre < centres) ? inj[((size_t)b * K + row) * centres + centre]
+                                                             : make_float2(0.f, __int_as_float(-1));
+                if constexpr (LIST) tabj[e] = jj;
+                else tab[e] = make_float4(cc.x, cc.y, jj.x, jj.y);
+            }
+            __syncthreads();
+            const int mine = LIST ? j >> 2 : (4 * j) >> s_shift, jpos = pos & ((1 << s_shift) - 1);
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) { // the expression of gn_maxpool_bwd_dx_kernel, bit for bit (rows beyond K stay zero)
+                const int row = q * 4 + kk;
+                if (row < K) { // (implies q < Kq; one predicate per row keeps the masks of 33 rows out of spilled SGPRs)
+                    const float4 t = pooled_table_row<LIST>(tab, tabj, tabc, cpw, row, mine);
+                    ogc_pooled_grad(xin[q], t.x, t.y, make_float2(t.z, t.w), jpos);
+                }
             }
         }
-    }
-    typedef short v4s __attribute__((ext_vector_type(4)));
-    constexpr int GQ = (KQ + 3) / 4;
-    v4s xb[BF ? GQ : 1][4]; // BF: the tile as packed bf16 operands (k-slot i of lane group kk = row 4 (4 g + i) + kk)
-    if constexpr (BF) {
-#pragma unroll
-        for (int g = 0; g < GQ; ++g) {
-            float4 r[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) r[i] = 4 * g + i < KQ ? xin[4 * g + i] : make_float4(0.f, 0.f, 0.f, 0.f);
-            xb[g][0] = ogc_pack_bf16_rr(r[0].x, r[1].x, r[2].x, r[3].x);
-            xb[g][1] = ogc_pack_bf16_rr(r[0].y, r[1].y, r[2].y, r[3].y);
-            xb[g][2] = ogc_pack_bf16_rr(r[0].z, r[1].z, r[2].z, r[3].z);
-            xb[g][3] = ogc_pack_bf16_rr(r[0].w, r[1].w, r[2].w, r[3].w);
-        }
-    }
-    for (int m0 = 0; m0 < M; m0 += 64) {
-        // FIRST: M <= 64 — the one row tile and the sample's coefficients are staged for the first position tile of the run and
-        // stay; the later tiles of the run meet no barrier and no dependent round trip besides their own loads
-        if (FIRST == 0 || it == 0) {
-        __syncthreads(); // previous tile fully consumed
+        typedef short v4s __attribute__((ext_vector_type(4)));
+        constexpr int GQ = (KQ + 3) / 4;
+        v4s xb[BF ? GQ : 1][4]; // BF: the tile as packed bf16 operands (k-slot i of lane group kk = row 4 (4 g + i) + kk)
         if constexpr (BF) {
-            ogc_stage_weight_tile_bf16<true, WG_WAVES, GQ>(a_lds, w, m0, M, K, Kq); // packed operands of w^T (conv_stage.h)
-        } else {
-            ogc_stage_weight_tile<true, WG_WAVES>(a_lds, w, m0, M, K, Kq);
-        }
-        for (int t = threadIdx.x; t < 64; t += WG_WAVES * OGC_WAVE) {
-            const int m = m0 + t;
-            const bool in = m < M;
-            cf[t * 5 + 0] = in ? pa[(size_t)b * M + m] : 0.f;
-            cf[t * 5 + 1] = in ? pb[(size_t)b * M + m] : 0.f;
-            cf[t * 5 + 2] = in ? coef[((size_t)b * M + m) * 3] : 0.f;
-            cf[t * 5 + 3] = in ? coef[((size_t)b * M + m) * 3 + 1] : 0.f;
-            cf[t * 5 + 4] = in ? coef[((size_t)b * M + m) * 3 + 2] : 0.f;
-        }
-        __syncthreads();
-        }
-        const int nblk = min(4, (M - m0 + 15) >> 4);
-        // One 16-row block of the tile at a time (unlike conv1x1_gemm_kernel, which runs the four blocks side by side): the
-        // block's accumulators are 16 registers instead of 64, its y_prev values (requested before its MFMA loop, consumed
-        // after it) another 16 — the epilogue needs both in VGPRs, and holding the whole tile there costs two wavefronts
-        // per SIMD.  Four independent accumulators (the four column blocks) keep the MFMA pipe issuing back to back.
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            if (a < nblk) {
-                float4 yv[4];
+            for (int g = 0; g < GQ; ++g) {
+                float4 r[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int m = m0 + a * 16 + kk * 4 + r;
-                    if constexpr (FIRST > 0) { // (rows beyond M meet zero weights, a wave that is not live zero x0 values)
-                        float w1r[FIRST];
-                        ogc_first_w1_row<FIRST>(w1r, s_w1, m);
-                        yv[r] = ogc_first_row<FIRST>(x0v, w1r);
-                    } else {
-                        yv[r] = (live && m < M) ? ogc_ld4(yb + (size_t)m * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-                }
-                v4f acc[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[c] = (v4f){0.f, 0.f, 0.f, 0.f};
+                for (int i = 0; i < 4; ++i) r[i] = 4 * g + i < KQ ? xin[4 * g + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+                xb[g][0] = ogc_pack_bf16_rr(r[0].x, r[1].x, r[2].x, r[3].x);
+                xb[g][1] = ogc_pack_bf16_rr(r[0].y, r[1].y, r[2].y, r[3].y);
+                xb[g][2] = ogc_pack_bf16_rr(r[0].z, r[1].z, r[2].z, r[3].z);
+                xb[g][3] = ogc_pack_bf16_rr(r[0].w, r[1].w, r[2].w, r[3].w);
+            }
+        }
+        for (int m0 = 0; m0 < M; m0 += 64) {
+            // FIRST: M <= 64 — the one row tile and the sample's coefficients are staged for the first position tile of the run and
+            // stay; the later tiles of the run meet no barrier and no dependent round trip besides their own loads
+            if (FIRST == 0 || it == 0) {
+                __syncthreads(); // previous tile fully consumed
                 if constexpr (BF) {
-                    // pairs of groups on v_mfma_f32_16x16x32_bf16, a single last group on the 16x16x16 form — the order of
-                    // conv1x1_gemm16_kernel's adjoint form (conv1x1_h.hip), so that the two kernels agree bit for bit
-                    const v4s *a_bf = reinterpret_cast<const v4s *>(a_lds);
-#pragma unroll
-                    for (int g = 0; g + 1 < GQ; g += 2) {
-                        if (4 * (g + 1) < Kq) {
-                            const v4s av0 = a_bf[(g * 64 + a * 16 + j) * 4 + kk], av1 = a_bf[((g + 1) * 64 + a * 16 + j) * 4 + kk];
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) acc[c] = ogc_mfma_bf16_k32(av0, av1, xb[g][c], xb[g + 1][c], acc[c]);
-                        } else if (4 * g < Kq) {
-                            const v4s av = a_bf[(g * 64 + a * 16 + j) * 4 + kk];
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(av, xb[g][c], acc[c], 0, 0, 0);
-                        }
-                    }
-                    if constexpr (GQ % 2 == 1) {
-                        constexpr int g = GQ - 1;
-                        if (4 * g < Kq) {
-                            const v4s av = a_bf[(g * 64 + a * 16 + j) * 4 + kk];
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(av, xb[g][c], acc[c], 0, 0, 0);
-                        }
-                    }
+                    ogc_stage_weight_tile_bf16<true, WG_WAVES, GQ>(a_lds, w, m0, M, K, Kq); // packed operands of w^T (conv_stage.h)
                 } else {
+                    ogc_stage_weight_tile<true, WG_WAVES>(a_lds, w, m0, M, K, Kq);
+                }
+                for (int t = threadIdx.x; t < 64; t += WG_WAVES * OGC_WAVE) {
+                    const int m = m0 + t;
+                    const bool in = m < M;
+                    cf[t * 5 + 0] = in ? pa[(size_t)b * M + m] : 0.f;
+                    cf[t * 5 + 1] = in ? pb[(size_t)b * M + m] : 0.f;
+                    cf[t * 5 + 2] = in ? coef[((size_t)b * M + m) * 3] : 0.f;
+                    cf[t * 5 + 3] = in ? coef[((size_t)b * M + m) * 3 + 1] : 0.f;
+                    cf[t * 5 + 4] = in ? coef[((size_t)b * M + m) * 3 + 2] : 0.f;
+                }
+                __syncthreads();
+            }
+            const int nblk = min(4, (M - m0 + 15) >> 4);
+            // One 16-row block of the tile at a time (unlike conv1x1_gemm_kernel, which runs the four blocks side by side): the
+            // block's accumulators are 16 registers instead of 64, its y_prev values (requested before its MFMA loop, consumed
+            // after it) another 16 — the epilogue needs both in VGPRs, and holding the whole tile there costs two wavefronts
+            // per SIMD.  Four independent accumulators (the four column blocks) keep the MFMA pipe issuing back to back.
 #pragma unroll
-                for (int q = 0; q < KQ; ++q) {
-                    if (q < Kq) {
-                        const float av = a_lds[(a * 16 + j) * a_ld + q * 4 + kk]; // A[m0+16a+j][4q+kk]
-                        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xin[q].x, acc[0], 0, 0, 0);
-                        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xin[q].y, acc[1], 0, 0, 0);
-                        acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xin[q].z, acc[2], 0, 0, 0);
-                        acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xin[q].w, acc[3], 0, 0, 0);
-                    }
-                }
-                }
-                if (live) { // (wave-uniform; m is uniform over the 16 lanes of a DPP row)
+            for (int a = 0; a < 4; ++a) {
+                if (a < nblk) {
+                    float4 yv[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int mi = a * 16 + kk * 4 + r, m = m0 + mi; // C/D layout: row (l >> 4) * 4 + r, column l & 15
-                        if (m < M) {
-                            const float fa = cf[mi * 5], fb = cf[mi * 5 + 1], al = cf[mi * 5 + 2], c2 = cf[mi * 5 + 3], c3 = cf[mi * 5 + 4];
-                            const float4 y = yv[r];
-                            float4 g = make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
-                            if (relu) {
-                                g.x = fmaf(fa, y.x, fb) > 0.f ? g.x : 0.f; g.y = fmaf(fa, y.y, fb) > 0.f ? g.y : 0.f;
-                                g.z = fmaf(fa, y.z, fb) > 0.f ? g.z : 0.f; g.w = fmaf(fa, y.w, fb) > 0.f ? g.w : 0.f;
+                        const int m = m0 + a * 16 + kk * 4 + r;
+                        if constexpr (FIRST > 0) { // (rows beyond M meet zero weights, a wave that is not live zero x0 values)
+                            float w1r[FIRST];
+                            ogc_first_w1_row<FIRST>(w1r, s_w1, m);
+                            yv[r] = ogc_first_row<FIRST>(x0v, w1r);
+                        } else {
+                            yv[r] = (live && m < M) ? ogc_ld4(yb + (size_t)m * hw + pos) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        }
+                    }
+                    v4f acc[4];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) acc[c] = (v4f){0.f, 0.f, 0.f, 0.f};
+                    if constexpr (BF) {
+                        // pairs of groups on v_mfma_f32_16x16x32_bf16, a single last group on the 16x16x16 form — the order of
+                        // conv1x1_gemm16_kernel's adjoint form (conv1x1_h.hip), so that the two kernels agree bit for bit
+                        const v4s *a_bf = reinterpret_cast<const v4s *>(a_lds);
+#pragma unroll
+                        for (int g = 0; g + 1 < GQ; g += 2) {
+                            if (4 * (g + 1) < Kq) {
+                                const v4s av0 = a_bf[(g * 64 + a * 16 + j) * 4 + kk], av1 = a_bf[((g + 1) * 64 + a * 16 + j) * 4 + kk];
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) acc[c] = ogc_mfma_bf16_k32(av0, av1, xb[g][c], xb[g + 1][c], acc[c]);
+                            } else if (4 * g < Kq) {
+                                const v4s av = a_bf[(g * 64 + a * 16 + j) * 4 + kk];
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(av, xb[g][c], acc[c], 0, 0, 0);
                             }
-                            float4 o;
-                            o.x = fmaf(al, g.x, fmaf(c2, y.x, c3)); o.y = fmaf(al, g.y, fmaf(c2, y.y, c3));
-                            o.z = fmaf(al, g.z, fmaf(c2, y.z, c3)); o.w = fmaf(al, g.w, fmaf(c2, y.w, c3));
-                            if constexpr (FIRST > 0) {
-                                float mine = 0.f; // lane j < c0 of the row keeps channel j's sum (every lane of the row holds them all)
-                                if constexpr (LIST) o.w *= wl; // (a lane without an entry holds zeros in x0v)
+                        }
+                        if constexpr (GQ % 2 == 1) {
+                            constexpr int g = GQ - 1;
+                            if (4 * g < Kq) {
+                                const v4s av = a_bf[(g * 64 + a * 16 + j) * 4 + kk];
 #pragma unroll
-                                for (int c = 0; c < FIRST; ++c) {
-                                    float d = fmaf(o.w, x0v[c].w, fmaf(o.z, x0v[c].z, fmaf(o.y, x0v[c].y, o.x * x0v[c].x)));
-                                    d += ogc_dpp_f32<0xB1>(d);
-                                    d += ogc_dpp_f32<0x4E>(d);
-                                    d += ogc_dpp_f32<0x141>(d);
-                                    d += ogc_dpp_f32<0x140>(d);
-                                    mine = j == c ? d : mine;
-                                }
-                                if (j < first.c0) atomicAdd(&s_dw[m * FC_MAX_C0 + j], mine);
-                            } else {
-                                if (mine_ok) ogc_st4(outb + (size_t)m * hw + pos, o);
-                                if constexpr (LIST && !POOLED) { // the skipped steps: the value of the entry's last position
-                                    const float v = ogc_dpp_f32<0xFF>(o.w); // (lane 3 of the quad of lanes that holds the entry)
+                                for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(av, xb[g][c], acc[c], 0, 0, 0);
+                            }
+                        }
+                    } else {
 #pragma unroll
-                                    for (int t = 1; t <= 3; ++t)
-                                        if (t <= skipped) ogc_st4(outb + (size_t)m * hw + pos + 16 * t, make_float4(v, v, v, v));
+                        for (int q = 0; q < KQ; ++q) {
+                            if (q < Kq) {
+                                const float av = a_lds[(a * 16 + j) * a_ld + q * 4 + kk]; // A[m0+16a+j][4q+kk]
+                                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xin[q].x, acc[0], 0, 0, 0);
+                                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xin[q].y, acc[1], 0, 0, 0);
+                                acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xin[q].z, acc[2], 0, 0, 0);
+                                acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xin[q].w, acc[3], 0, 0, 0);
+                            }
+                        }
+                    }
+                    if (live) { // (wave-uniform; m is uniform over the 16 lanes of a DPP row)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int mi = a * 16 + kk * 4 + r, m = m0 + mi; // C/D layout: row (l >> 4) * 4 + r, column l & 15
+                            if (m < M) {
+                                const float fa = cf[mi * 5], fb = cf[mi * 5 + 1], al = cf[mi * 5 + 2], c2 = cf[mi * 5 + 3], c3 = cf[mi * 5 + 4];
+                                float4 o = make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
+                                ogc_gn_adjoint(o, yv[r], fa, fb, al, c2, c3, relu);
+                                if constexpr (FIRST > 0) {
+                                    float mine = 0.f; // lane j < c0 of the row keeps channel j's sum (every lane of the row holds them all)
+                                    if constexpr (LIST) o.w *= wl; // (a lane without an entry holds zeros in x0v)
+#pragma unroll
+                                    for (int c = 0; c < FIRST; ++c) {
+                                        float d = fmaf(o.w, x0v[c].w, fmaf(o.z, x0v[c].z, fmaf(o.y, x0v[c].y, o.x * x0v[c].x)));
+                                        d += ogc_dpp_f32<0xB1>(d);
+                                        d += ogc_dpp_f32<0x4E>(d);
+                                        d += ogc_dpp_f32<0x141>(d);
+                                        d += ogc_dpp_f32<0x140>(d);
+                                        mine = j == c ? d : mine;
+                                    }
+                                    if (j < first.c0) atomicAdd(&s_dw[m * FC_MAX_C0 + j], mine);
+                                } else {
+                                    if (mine_ok) ogc_st4(outb + (size_t)m * hw + pos, o);
+                                    if constexpr (LIST && !POOLED) { // the skipped steps: the value of the entry's last position
+                                        const float v = ogc_dpp_f32<0xFF>(o.w); // (lane 3 of the quad of lanes that holds the entry)
+#pragma unroll
+                                        for (int t = 1; t <= 3; ++t)
+                                            if (t <= skipped) ogc_st4(outb + (size_t)m * hw + pos + 16 * t, make_float4(v, v, v, v));
+                                    }
                                 }
                             }
                         }
@@ -872,7 +615,6 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
                 }
             }
         }
-    }
     }
     if constexpr (FIRST > 0) {
         __syncthreads();
@@ -887,6 +629,26 @@ __global__ __launch_bounds__(WG_WAVES *OGC_WAVE) void dgrad_adjoint_kernel(int M
 
 namespace {
 int nsample_shift(int nsample) { return nsample == 16 ? 4 : nsample == 32 ? 5 : nsample == 64 ? 6 : -1; }
+
+// The pooled forms' own preconditions (grad_y in the sparse form of ogc_group_norm_maxpool_bwd_sparse: y (B, cout, hw) is the
+// convolution's output, hw = centres * nsample); sh: log2 nsample.
+int pooled_check(const char *name, int b, int hw, int nsample, const float *coef2, const float *inj, int &sh) {
+    sh = nsample_shift(nsample);
+    if (sh < 0 || hw % nsample != 0 || (((uintptr_t)coef2 | (uintptr_t)inj) & 7) != 0) {
+        ogc_set_error("%s: nsample=%d must be 16, 32 or 64 and divide hw=%d", name, nsample, hw);
+        return OGC_ERR_UNSUPPORTED;
+    }
+    OGC_REQUIRE(b == 0 || (coef2 && inj), "%s: null pointer", name);
+    return OGC_OK;
+}
+
+// The list forms' entry: the list checked (live_steps.h) ahead of everything else, then run(name, list).
+template <typename F>
+int with_live(const char *name, const int *live, const int *n_live, int live_cap, int hw, int nsample, F run) {
+    LiveIn ls;
+    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
+    return rc != OGC_OK ? rc : run(name, ls);
+}
 
 template <typename AT>
 int wgrad_moments_impl(const char *name, int b, int cin, int cout, int hw, int relu, const AT *y_prev, const float *pa,
@@ -904,24 +666,20 @@ int wgrad_moments_impl(const char *name, int b, int cin, int cout, int hw, int r
     }
     OGC_REQUIRE((long long)cin * hw < (1ll << 31) && (long long)cout * hw < (1ll << 31) && b <= 32768,
                 "%s: one sample exceeds 32-bit indexing", name);
-    hipStream_t s = (hipStream_t)stream;
     if (b == 0) return OGC_OK;
-    if (ogc_zero_async(moments, sizeof(float) * 2 * (size_t)b * cin * cout, s) != hipSuccess) {
-        ogc_set_error("%s: memset failed", name);
-        return OGC_ERR_LAUNCH;
-    }
-#define OGC_ML(A, C) moments_launch<A, C, AT>(b, cin, cout, hw, relu, y_prev, grad_y, pa, pb, coef2, inj, s_shift, moments, s, FirstIn(), ls)
-    if (cout <= 16 && cin <= 16) OGC_ML(1, 1);
-    else if (cout <= 32 && cin <= 16) OGC_ML(2, 1);
-    else if (cout <= 32 && cin <= 32) OGC_ML(2, 2);
-    else if (cin <= 16) OGC_ML(4, 1);
-    else if (cin <= 32) OGC_ML(4, 2);
-    else if (cout <= 32) OGC_ML(2, 4);
-    else if (inj && sizeof(AT) == 4) OGC_ML(4, 2); // the pooled fp32 <4, 4> instantiation runs out of registers (256 + 34): two column tiles instead
-    else OGC_ML(4, 4);
-#undef OGC_ML
-    OGC_CHECK_LAUNCH(name);
-    return OGC_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (inj) return moments_run<AT, 0, true>(name, b, cin, cout, hw, relu, y_prev, grad_y, pa, pb, coef2, inj, s_shift, moments, s, FirstIn(), ls);
+    return moments_run<AT, 0, false>(name, b, cin, cout, hw, relu, y_prev, grad_y, pa, pb, coef2, inj, s_shift, moments, s, FirstIn(), ls);
+}
+
+template <typename AT>
+int wgrad_moments_pooled_impl(const char *name, int b, int cin, int cout, int hw, int relu, int nsample, const AT *y_prev,
+                              const float *pa, const float *pb, const AT *y, const float *coef2, const float *inj,
+                              float *moments, ogc_stream_t stream, LiveIn ls = LiveIn()) {
+    int sh;
+    const int rc = pooled_check(name, b, hw, nsample, coef2, inj, sh);
+    if (rc != OGC_OK) return rc;
+    return wgrad_moments_impl<AT>(name, b, cin, cout, hw, relu, y_prev, pa, pb, y, coef2, inj, sh, moments, stream, ls);
 }
 } // namespace
 
@@ -937,23 +695,7 @@ extern "C" int ogc_conv1x1_wgrad_moments_h(int b, int cin, int cout, int hw, int
                                         nullptr, 0, moments, stream);
 }
 
-// The same with grad_y in the sparse form of ogc_group_norm_maxpool_bwd_sparse: y (B, cout, hw) is the convolution's output,
-// hw = centres * nsample (nsample 16, 32 or 64).
-namespace {
-template <typename AT>
-int wgrad_moments_pooled_impl(const char *name, int b, int cin, int cout, int hw, int relu, int nsample, const AT *y_prev,
-                              const float *pa, const float *pb, const AT *y, const float *coef2, const float *inj,
-                              float *moments, ogc_stream_t stream, LiveIn ls = LiveIn()) {
-    const int sh = nsample_shift(nsample);
-    if (sh < 0 || hw % nsample != 0 || (((uintptr_t)coef2 | (uintptr_t)inj) & 7) != 0) {
-        ogc_set_error("%s: nsample=%d must be 16, 32 or 64 and divide hw=%d", name, nsample, hw);
-        return OGC_ERR_UNSUPPORTED;
-    }
-    OGC_REQUIRE(b == 0 || (coef2 && inj), "%s: null pointer", name);
-    return wgrad_moments_impl<AT>(name, b, cin, cout, hw, relu, y_prev, pa, pb, y, coef2, inj, sh, moments, stream, ls);
-}
-} // namespace
-
+// The same with grad_y in the sparse form (pooled_check above); nsample 16, 32 or 64.
 extern "C" int ogc_conv1x1_wgrad_moments_pooled(int b, int cin, int cout, int hw, int relu, int nsample, const float *y_prev,
                                                 const float *pa, const float *pb, const float *y, const float *coef2,
                                                 const float *inj, float *moments, ogc_stream_t stream) {
@@ -965,11 +707,9 @@ extern "C" int ogc_conv1x1_wgrad_moments_pooled_live(int b, int cin, int cout, i
                                                      const float *pa, const float *pb, const float *y, const float *coef2,
                                                      const float *inj, const int *live, const int *n_live, int live_cap,
                                                      float *moments, ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_wgrad_moments_pooled_live";
-    LiveIn ls;
-    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
-    if (rc != OGC_OK) return rc;
-    return wgrad_moments_pooled_impl<float>(name, b, cin, cout, hw, relu, nsample, y_prev, pa, pb, y, coef2, inj, moments, stream, ls);
+    return with_live("ogc_conv1x1_wgrad_moments_pooled_live", live, n_live, live_cap, hw, nsample, [&](const char *name, const LiveIn &ls) {
+        return wgrad_moments_pooled_impl<float>(name, b, cin, cout, hw, relu, nsample, y_prev, pa, pb, y, coef2, inj, moments, stream, ls);
+    });
 }
 
 extern "C" int ogc_conv1x1_wgrad_moments_pooled_h(int b, int cin, int cout, int hw, int relu, int nsample,
@@ -1000,6 +740,45 @@ extern "C" int ogc_gn_moments_combine(int b, int cin, int cout, int hw, int grou
 }
 
 namespace {
+// One launch of dgrad_adjoint_kernel: KQ by the width of g_y, then the form by what came along — a first convolution (FIRST), a
+// live-step list (fp32 only), the sparse gradient (inj).
+template <typename AT, int FIRST>
+void dgrad_launch(dim3 grid, size_t lds, hipStream_t s, int M, int K, int hw, int relu, const float *w, const AT *gy, const AT *yprev,
+                  const float *pa, const float *pb, const float *coef, const float *coef2, const float *inj, int s_shift, AT *out,
+                  const FirstIn &first, const LiveIn &ls) {
+    constexpr bool BF = sizeof(AT) == 2;
+    const float2 *c2 = reinterpret_cast<const float2 *>(coef2), *ij = reinterpret_cast<const float2 *>(inj);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, relu, w, gy, yprev, pa, pb, coef, c2, ij, s_shift,
+                           out, first, ls);
+    };
+    auto form = [&](auto kq) {
+        constexpr int KQ = decltype(kq)::value;
+        if constexpr (FIRST > 0) { // (list form: the run of tiles derived on the device)
+            if (ls.steps) go(dgrad_adjoint_kernel<KQ, false, AT, false, FIRST, true>);
+            else go(dgrad_adjoint_kernel<KQ, false, AT, false, FIRST>);
+        } else {
+            if constexpr (!BF) {
+                if (ls.steps) { // (grid of the worst case; workgroups beyond the list leave at once)
+                    if (inj) go(dgrad_adjoint_kernel<KQ, true, AT, false, 0, true>);
+                    else go(dgrad_adjoint_kernel<KQ, false, AT, false, 0, true>); // (the plain list form: dense output, s_shift bounds the filled steps)
+                    return;
+                }
+            }
+            if (inj) go(dgrad_adjoint_kernel<KQ, true, AT, BF>);
+            else go(dgrad_adjoint_kernel<KQ, false, AT, BF>);
+        }
+    };
+    const int Kq = (K + 3) / 4;
+    if (Kq <= 8) form(TileC<8>());
+    else if (Kq <= 16 || FIRST > 0) form(TileC<16>()); // (FIRST: K <= 64, checked by the entry point)
+    else if constexpr (FIRST == 0) {
+        if (Kq <= 25) form(TileC<25>());
+        else if (Kq <= 33) form(TileC<33>());
+        else form(TileC<40>());
+    }
+}
+
 template <typename AT>
 int dgrad_adjoint_impl(const char *name, int b, int cin, int cout, int hw, int relu, const float *w, const AT *grad_y,
                        const AT *y_prev, const float *pa, const float *pb, const float *coef, const float *coef2,
@@ -1034,36 +813,19 @@ int dgrad_adjoint_impl(const char *name, int b, int cin, int cout, int hw, int r
             return OGC_OK;
         }
     }
-    const float2 *c2 = reinterpret_cast<const float2 *>(coef2), *ij = reinterpret_cast<const float2 *>(inj);
-#define OGC_DGA(KQV)                                                                                                        \
-    do {                                                                                                                    \
-        if constexpr (sizeof(AT) == 4) {                                                                                    \
-            if (inj && ls.steps) { /* (grid of the worst case; workgroups beyond the list leave at once) */                \
-                hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, true, AT, false, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, \
-                                   hw, relu, w, grad_y, y_prev, pa, pb, coef, c2, ij, s_shift, grad_prev, FirstIn(), ls);  \
-                break;                                                                                                      \
-            }                                                                                                               \
-            if (ls.steps) { /* (the plain list form: dense output, s_shift bounds the filled steps) */                     \
-                hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, AT, false, 0, true>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, \
-                                   hw, relu, w, grad_y, y_prev, pa, pb, coef, c2, ij, s_shift, grad_prev, FirstIn(), ls);  \
-                break;                                                                                                      \
-            }                                                                                                               \
-        }                                                                                                                   \
-        if (inj)                                                                                                            \
-            hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, true, AT, sizeof(AT) == 2>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, relu, w,  \
-                               grad_y, y_prev, pa, pb, coef, c2, ij, s_shift, grad_prev);                                  \
-        else                                                                                                                \
-            hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, AT, sizeof(AT) == 2>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, hw, relu, w, \
-                               grad_y, y_prev, pa, pb, coef, c2, ij, 0, grad_prev);                                        \
-    } while (0)
-    if (Kq <= 8) OGC_DGA(8);
-    else if (Kq <= 16) OGC_DGA(16);
-    else if (Kq <= 25) OGC_DGA(25);
-    else if (Kq <= 33) OGC_DGA(33);
-    else OGC_DGA(40);
-#undef OGC_DGA
+    dgrad_launch<AT, 0>(grid, lds, s, M, K, hw, relu, w, grad_y, y_prev, pa, pb, coef, coef2, inj, s_shift, grad_prev, FirstIn(), ls);
     OGC_CHECK_LAUNCH(name);
     return OGC_OK;
+}
+
+template <typename AT>
+int dgrad_adjoint_pooled_impl(const char *name, int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
+                              const AT *y, const float *coef2, const float *inj, const AT *y_prev, const float *pa,
+                              const float *pb, const float *coef, AT *grad_prev, ogc_stream_t stream, LiveIn ls = LiveIn()) {
+    int sh;
+    const int rc = pooled_check(name, b, hw, nsample, coef2, inj, sh);
+    if (rc != OGC_OK) return rc;
+    return dgrad_adjoint_impl<AT>(name, b, cin, cout, hw, relu, w, y, y_prev, pa, pb, coef, coef2, inj, sh, grad_prev, stream, ls);
 }
 } // namespace
 
@@ -1081,22 +843,7 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_h(int b, int cin, int cout, int hw, int
                                         nullptr, nullptr, 0, grad_prev, stream);
 }
 
-// The same with grad_y in the sparse form of ogc_group_norm_maxpool_bwd_sparse (y: the convolution's output).
-namespace {
-template <typename AT>
-int dgrad_adjoint_pooled_impl(const char *name, int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
-                              const AT *y, const float *coef2, const float *inj, const AT *y_prev, const float *pa,
-                              const float *pb, const float *coef, AT *grad_prev, ogc_stream_t stream, LiveIn ls = LiveIn()) {
-    const int sh = nsample_shift(nsample);
-    if (sh < 0 || hw % nsample != 0 || (((uintptr_t)coef2 | (uintptr_t)inj) & 7) != 0) {
-        ogc_set_error("%s: nsample=%d must be 16, 32 or 64 and divide hw=%d", name, nsample, hw);
-        return OGC_ERR_UNSUPPORTED;
-    }
-    OGC_REQUIRE(b == 0 || (coef2 && inj), "%s: null pointer", name);
-    return dgrad_adjoint_impl<AT>(name, b, cin, cout, hw, relu, w, y, y_prev, pa, pb, coef, coef2, inj, sh, grad_prev, stream, ls);
-}
-} // namespace
-
+// The same with grad_y in the sparse form (y: the convolution's output).
 extern "C" int ogc_conv1x1_dgrad_adjoint_pooled(int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
                                                 const float *y, const float *coef2, const float *inj, const float *y_prev,
                                                 const float *pa, const float *pb, const float *coef, float *grad_prev,
@@ -1109,12 +856,10 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_pooled_live(int b, int cin, int cout, i
                                                      const float *y, const float *coef2, const float *inj, const float *y_prev,
                                                      const float *pa, const float *pb, const float *coef, const int *live,
                                                      const int *n_live, int live_cap, float *grad_prev, ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_dgrad_adjoint_pooled_live";
-    LiveIn ls;
-    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
-    if (rc != OGC_OK) return rc;
-    return dgrad_adjoint_pooled_impl<float>(name, b, cin, cout, hw, relu, nsample, w, y, coef2, inj, y_prev, pa, pb, coef, grad_prev,
-                                            stream, ls);
+    return with_live("ogc_conv1x1_dgrad_adjoint_pooled_live", live, n_live, live_cap, hw, nsample, [&](const char *name, const LiveIn &ls) {
+        return dgrad_adjoint_pooled_impl<float>(name, b, cin, cout, hw, relu, nsample, w, y, coef2, inj, y_prev, pa, pb, coef, grad_prev,
+                                                stream, ls);
+    });
 }
 
 extern "C" int ogc_conv1x1_dgrad_adjoint_pooled_h(int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
@@ -1138,31 +883,15 @@ int wgrad_moments_first_impl(const char *name, int b, int cin, int cout, int hw,
         return OGC_ERR_UNSUPPORTED;
     }
     OGC_REQUIRE((long long)cout * hw < (1ll << 31), "%s: one sample exceeds 32-bit indexing", name);
-    hipStream_t s = (hipStream_t)stream;
     if (b == 0) return OGC_OK;
-    if (ogc_zero_async(moments, sizeof(float) * 2 * (size_t)b * cin * cout, s) != hipSuccess) {
-        ogc_set_error("%s: memset failed", name);
-        return OGC_ERR_LAUNCH;
-    }
+    hipStream_t s = (hipStream_t)stream;
     FirstIn first;
     first.x0 = x0; first.w1 = w1; first.c0 = c0;
     const int cp = ogc_first_cp(c0);
-    // (at most two 16-column blocks per workgroup: beyond 32 channels of y1 the grid's z dimension walks the column tiles — the
-    // recomputed operand costs registers the <.., 4> forms do not have)
-#define OGC_MLF(A, C)                                                                                                                    \
-    do {                                                                                                                                 \
-        if (cp == 3) moments_launch<A, C, float, 3>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first, ls); \
-        else if (cp == 6) moments_launch<A, C, float, 6>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first, ls); \
-        else moments_launch<A, C, float, 8>(b, cin, cout, hw, relu, nullptr, grad_y, pa, pb, nullptr, nullptr, 0, moments, s, first, ls); \
-    } while (0)
-    if (cout <= 16 && cin <= 16) OGC_MLF(1, 1);
-    else if (cout <= 32 && cin <= 16) OGC_MLF(2, 1);
-    else if (cout <= 32) OGC_MLF(2, 2);
-    else if (cin <= 16) OGC_MLF(4, 1);
-    else OGC_MLF(4, 2);
-#undef OGC_MLF
-    OGC_CHECK_LAUNCH(name);
-    return OGC_OK;
+    const float *none = nullptr;
+    if (cp == 3) return moments_run<float, 3, false>(name, b, cin, cout, hw, relu, none, grad_y, pa, pb, none, none, 0, moments, s, first, ls);
+    if (cp == 6) return moments_run<float, 6, false>(name, b, cin, cout, hw, relu, none, grad_y, pa, pb, none, none, 0, moments, s, first, ls);
+    return moments_run<float, 8, false>(name, b, cin, cout, hw, relu, none, grad_y, pa, pb, none, none, 0, moments, s, first, ls);
 }
 
 int dgrad_adjoint_first_impl(const char *name, int b, int cin, int cout, int hw, int relu, int c0, const float *w,
@@ -1193,26 +922,12 @@ int dgrad_adjoint_first_impl(const char *name, int b, int cin, int cout, int hw,
     FirstIn first;
     first.x0 = x0; first.w1 = w1; first.c0 = c0; first.dw1 = grad_w1;
     first.run = ogc_divup(tiles, chunks);
-    dim3 grid(ogc_divup(tiles, first.run), b);
+    dim3 grid(ogc_divup(tiles, first.run), b); // (list form: the same grid — the worst case, every step live, is as many tiles)
     const int cp = ogc_first_cp(c0);
-    // (list form: the same grid — the worst case, every step live, is as many tiles — and the run derived on the device)
-#define OGC_DGAF(KQV, CPV)                                                                                                  \
-    do {                                                                                                                    \
-        if (ls.steps)                                                                                                       \
-            hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, float, false, CPV, true>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, \
-                               K, hw, relu, w, grad_y, (const float *)nullptr, pa, pb, coef, (const float2 *)nullptr,       \
-                               (const float2 *)nullptr, 0, (float *)nullptr, first, ls);                                    \
-        else                                                                                                                \
-            hipLaunchKernelGGL((dgrad_adjoint_kernel<KQV, false, float, false, CPV>), grid, dim3(WG_WAVES * OGC_WAVE), lds, s, M, K, \
-                               hw, relu, w, grad_y, (const float *)nullptr, pa, pb, coef, (const float2 *)nullptr,          \
-                               (const float2 *)nullptr, 0, (float *)nullptr, first, ls);                                    \
-    } while (0)
-    if (Kq <= 8) {
-        if (cp == 3) OGC_DGAF(8, 3); else if (cp == 6) OGC_DGAF(8, 6); else OGC_DGAF(8, 8);
-    } else {
-        if (cp == 3) OGC_DGAF(16, 3); else if (cp == 6) OGC_DGAF(16, 6); else OGC_DGAF(16, 8);
-    }
-#undef OGC_DGAF
+    const float *none = nullptr;
+    if (cp == 3) dgrad_launch<float, 3>(grid, lds, s, M, K, hw, relu, w, grad_y, none, pa, pb, coef, none, none, 0, (float *)nullptr, first, ls);
+    else if (cp == 6) dgrad_launch<float, 6>(grid, lds, s, M, K, hw, relu, w, grad_y, none, pa, pb, coef, none, none, 0, (float *)nullptr, first, ls);
+    else dgrad_launch<float, 8>(grid, lds, s, M, K, hw, relu, w, grad_y, none, pa, pb, coef, none, none, 0, (float *)nullptr, first, ls);
     OGC_CHECK_LAUNCH(name);
     return OGC_OK;
 }
@@ -1237,22 +952,18 @@ extern "C" int ogc_conv1x1_wgrad_moments_first_live(int b, int cin, int cout, in
                                                     const float *w1, const float *pa, const float *pb, const float *grad_y,
                                                     const int *live, const int *n_live, int live_cap, float *moments,
                                                     ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_wgrad_moments_first_live";
-    LiveIn ls;
-    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
-    if (rc != OGC_OK) return rc;
-    return wgrad_moments_first_impl(name, b, cin, cout, hw, relu, c0, x0, w1, pa, pb, grad_y, moments, stream, ls);
+    return with_live("ogc_conv1x1_wgrad_moments_first_live", live, n_live, live_cap, hw, nsample, [&](const char *name, const LiveIn &ls) {
+        return wgrad_moments_first_impl(name, b, cin, cout, hw, relu, c0, x0, w1, pa, pb, grad_y, moments, stream, ls);
+    });
 }
 
 extern "C" int ogc_conv1x1_dgrad_adjoint_first_live(int b, int cin, int cout, int hw, int relu, int c0, int nsample, const float *w,
                                                     const float *grad_y, const float *x0, const float *w1, const float *pa,
                                                     const float *pb, const float *coef, const int *live, const int *n_live,
                                                     int live_cap, float *grad_w1, ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_dgrad_adjoint_first_live";
-    LiveIn ls;
-    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
-    if (rc != OGC_OK) return rc;
-    return dgrad_adjoint_first_impl(name, b, cin, cout, hw, relu, c0, w, grad_y, x0, w1, pa, pb, coef, grad_w1, stream, ls);
+    return with_live("ogc_conv1x1_dgrad_adjoint_first_live", live, n_live, live_cap, hw, nsample, [&](const char *name, const LiveIn &ls) {
+        return dgrad_adjoint_first_impl(name, b, cin, cout, hw, relu, c0, w, grad_y, x0, w1, pa, pb, coef, grad_w1, stream, ls);
+    });
 }
 
 // The plain list forms — a middle layer between a pooled tail in list form and a layer that reads its gradient densely: grad_y and
@@ -1261,59 +972,17 @@ extern "C" int ogc_conv1x1_dgrad_adjoint_first_live(int b, int cin, int cout, in
 extern "C" int ogc_conv1x1_wgrad_moments_live(int b, int cin, int cout, int hw, int relu, int nsample, const float *y_prev,
                                               const float *pa, const float *pb, const float *grad_y, const int *live,
                                               const int *n_live, int live_cap, float *moments, ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_wgrad_moments_live";
-    LiveIn ls;
-    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
-    if (rc != OGC_OK) return rc;
-    return wgrad_moments_impl<float>(name, b, cin, cout, hw, relu, y_prev, pa, pb, grad_y, nullptr, nullptr, 0, moments, stream, ls);
+    return with_live("ogc_conv1x1_wgrad_moments_live", live, n_live, live_cap, hw, nsample, [&](const char *name, const LiveIn &ls) {
+        return wgrad_moments_impl<float>(name, b, cin, cout, hw, relu, y_prev, pa, pb, grad_y, nullptr, nullptr, 0, moments, stream, ls);
+    });
 }
 
 extern "C" int ogc_conv1x1_dgrad_adjoint_live_fill(int b, int cin, int cout, int hw, int relu, int nsample, const float *w,
                                                    const float *grad_y, const float *y_prev, const float *pa, const float *pb,
                                                    const float *coef, const int *live, const int *n_live, int live_cap,
                                                    float *grad_prev, ogc_stream_t stream) {
-    const char *name = "ogc_conv1x1_dgrad_adjoint_live_fill";
-    LiveIn ls;
-    const int rc = live_check(name, live, n_live, live_cap, hw, nsample, ls);
-    if (rc != OGC_OK) return rc;
-    return dgrad_adjoint_impl<float>(name, b, cin, cout, hw, relu, w, grad_y, y_prev, pa, pb, coef, nullptr, nullptr,
-                                     nsample_shift(nsample), grad_prev, stream, ls);
-}
-
-// live (b, p * s / 16), n_live (b): the live-step list of a neighbour list idx (b, p, s) (LiveIn above).
-extern "C" int ogc_live_steps(int b, int p, int s, const int *idx, int *live, int *n_live, ogc_stream_t stream) {
-    OGC_REQUIRE(b >= 0 && p >= 1, "ogc_live_steps: bad shape");
-    if (s != 16 && s != 32 && s != 64) {
-        ogc_set_error("ogc_live_steps: nsample=%d must be 16, 32 or 64", s);
-        return OGC_ERR_UNSUPPORTED;
-    }
-    OGC_REQUIRE(idx && live && n_live, "ogc_live_steps: null pointer");
-    if (p > LIVE_MAX_P) {
-        ogc_set_error("ogc_live_steps: p=%d centres per sample, at most %d", p, LIVE_MAX_P);
-        return OGC_ERR_UNSUPPORTED;
-    }
-    if (b == 0) return OGC_OK;
-    hipLaunchKernelGGL(live_steps_kernel<false>, dim3(b), dim3(1024), 0, (hipStream_t)stream, p, s, idx, live, n_live);
-    OGC_CHECK_LAUNCH("ogc_live_steps");
-    return OGC_OK;
-}
-
-// ogc_live_steps, and in the same launch the forward list fwd (b, p * s / 16), n_fwd (b) (live_steps.h): the same entries packed so
-// that no 64-position group crosses a tile of four entries.  s in {32, 64}, p * s a multiple of 64.
-extern "C" int ogc_live_steps_fwd(int b, int p, int s, const int *idx, int *live, int *n_live, int *fwd, int *n_fwd,
-                                  ogc_stream_t stream) {
-    OGC_REQUIRE(b >= 0 && p >= 1, "ogc_live_steps_fwd: bad shape");
-    if ((s != 32 && s != 64) || (p * (long long)s) % 64 != 0) {
-        ogc_set_error("ogc_live_steps_fwd: needs nsample 32 or 64 and p * nsample %% 64 == 0 (p=%d, nsample=%d)", p, s);
-        return OGC_ERR_UNSUPPORTED;
-    }
-    OGC_REQUIRE(idx && live && n_live && fwd && n_fwd, "ogc_live_steps_fwd: null pointer");
-    if (p > LIVE_MAX_P) {
-        ogc_set_error("ogc_live_steps_fwd: p=%d centres per sample, at most %d", p, LIVE_MAX_P);
-        return OGC_ERR_UNSUPPORTED;
-    }
-    if (b == 0) return OGC_OK;
-    hipLaunchKernelGGL(live_steps_kernel<true>, dim3(b), dim3(1024), 0, (hipStream_t)stream, p, s, idx, live, n_live, fwd, n_fwd);
-    OGC_CHECK_LAUNCH("ogc_live_steps_fwd");
-    return OGC_OK;
+    return with_live("ogc_conv1x1_dgrad_adjoint_live_fill", live, n_live, live_cap, hw, nsample, [&](const char *name, const LiveIn &ls) {
+        return dgrad_adjoint_impl<float>(name, b, cin, cout, hw, relu, w, grad_y, y_prev, pa, pb, coef, nullptr, nullptr,
+                                         nsample_shift(nsample), grad_prev, stream, ls);
+    });
 }

@@ -1,5 +1,5 @@
 // live_steps.h — the live-step lists of a first level's neighbour lists: what the list forms of the chain's kernels share
-// (backward: gn_fused_bwd.hip, where live_steps_kernel makes the lists; forward: conv1x1.hip).
+// (backward: gn_fused_bwd.hip; forward: conv1x1.hip), and live_steps.hip, where live_steps_kernel makes the lists.
 //
 // A neighbour list idx (B, P, S) ends in repeats of its first entry wherever the search found fewer than S points inside the
 // radius (utils/pointnet2_util.py:59-79).  Every kernel of a level's chain is column-wise, so those columns carry bit-equal
