@@ -55,7 +55,8 @@ enum {
  * ogc_soft_carry likewise: a new entry point, no prototype changed.  ogc_scan_crop_camera / _front / _tile and ogc_box_segm /
  * _chunk likewise.  ogc_kittisf_unproject and ogc_png_unfilter likewise.  ogc_live_steps_fwd, ogc_conv1x1_gemm_affine_first_live
  * and ogc_conv1x1_gemm_affine_pool_live likewise.  ogc_moving_stats / _label_cap likewise.  ogc_surface_candidates, ogc_surface_thin /
- * _ws_bytes and ogc_nearest_label likewise.  ogc_depth_render / _ws_bytes / _timed and ogc_depth_points likewise. */
+ * _ws_bytes and ogc_nearest_label likewise.  ogc_depth_render / _ws_bytes / _timed and ogc_depth_points likewise.
+ * ogc_slot_confidence likewise. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -327,6 +328,34 @@ int ogc_seg_eval_ignore(int B, int n, int k, const int *segm, const float *mask,
  * launched.  B == 0 is a no-op whatever else is passed. */
 int ogc_flow_eval(int B, int N, const float *gt_flow, const float *flow_pred, double epe_norm_thresh, double eps,
                   double *epe_sum, int *counts, ogc_stream_t stream);
+
+/* The confidences of predicted segmentations, for training on them (datasets.py load_prediction / load_confidence), in one
+ * launch and without ground truth.  mask (B,n,k) f32 point-major.  Per sample, the PRESENT slots are those that own at least one
+ * point, in ascending slot index, numbered j = 0 .. n_object-1: the order in which compress_label_id numbers the saved arg-max
+ * labels when a reader loads them.  Outputs, which do not depend on their previous contents:
+ *   hard (B,n) i32      arg-max over the k slots by the rule of ogc_seg_eval: the first maximum; a NaN counts as the maximum and
+ *                       the first NaN wins.  May be NULL: then it is not written, and nothing else changes.
+ *   slots (B,k) i32     the slot index of the j-th present slot; -1 for j >= n_object.
+ *   sizes (B,k) i32     its number of points; 0 for j >= n_object.
+ *   conf (B,k) f32      (float)(S / sizes), rounded once, S the fp64 sum of the widened mask[b,p,slot] over the slot's own points
+ *                       (metrics/seg_metric.py:81-85 for a prediction, without the validity filter of eval_segm and without the
+ *                       column quirk that ogc_seg_eval keeps); 0 for j >= n_object.
+ *   n_object (B) i32    the number of present slots, >= 1.
+ * A NaN makes the confidence of the slot that owns its point NaN; every other slot and every other sample is untouched.
+ * The sums are formed in a fixed order (per-workgroup partials, one ordered finish; no floating-point atomics): identical bits
+ * from call to call and from process to process.  A workgroup takes OGC_SLOT_CONF_TILE points of one sample, so a sample spans
+ * ceil(n / OGC_SLOT_CONF_TILE) workgroups and its bits depend on n alone — unless n > OGC_SLOT_CONF_TILE and B times that number
+ * exceeds OGC_SLOT_CONF_MAX_PARTIALS: then a workgroup takes several consecutive tiles and the order, still fixed, is a
+ * function of (B, n).  One kernel launch, no allocation, no fill, no synchronisation: capturable.  Several workgroups per sample
+ * exchange their partials through a static table of the library, as ogc_flow_eval's do: calls on DIFFERENT streams of one device
+ * must not overlap in time (stream order is all that is needed between calls).
+ * 1 <= k <= OGC_SLOT_CONF_MAX_K, n >= 1, no null pointer other than hard: OGC_ERR_INVALID_ARG otherwise, nothing launched.
+ * B == 0 is a no-op whatever else is passed. */
+#define OGC_SLOT_CONF_MAX_K 64
+#define OGC_SLOT_CONF_TILE 1024
+#define OGC_SLOT_CONF_MAX_PARTIALS 2048
+int ogc_slot_confidence(int B, int n, int k, const float *mask, int *hard, int *slots, int *sizes, float *conf, int *n_object,
+                        ogc_stream_t stream);
 
 /* The supervised mask loss (losses/seg_loss_sup.py) without its (B, N, K, K) tensors.  Throughout: mask (B,n,k) f32 point-major,
  * the model's soft masks; gt_mask (B,n,k) f32 with entries in [0, 1], not necessarily 0/1 (batch_segm_to_mask_withconf scales

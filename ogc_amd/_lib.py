@@ -70,6 +70,7 @@ SIGNATURES = {
     "ogc_seg_eval": [_int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_seg_eval_ignore": [_int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_flow_eval": [_int, _int, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp],
+    "ogc_slot_confidence": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_lsap_maximize": [_int, _int, _vp, _vp, _vp],
     "ogc_sup_loss_ws_doubles": [_int, _int, _int],
     "ogc_sup_match_cost": [_int, _int, _int, _vp, _vp, _vp, _int, _dbl, _dbl, _vp, _vp, _vp, _vp],

@@ -26,10 +26,13 @@ one directory tree:
   KITTIDetectionDataset      <root>/downsampled/<id>/{pc,segm}.npy, a split file listing the ids (datasets/dataset_kittidet.py)
   SemanticKITTIDataset       the same files; the ids are the sorted directory names whose first two characters are a sequence
                              number in `sequence_list` (datasets/dataset_semantickitti.py).  Both are single-frame sets for
-                             evaluation (test_seg.py): the frame is duplicated to two views, the flows are zero
+                             evaluation (test_seg.py): the frame is duplicated to two views, the flows are zero.
+                             KITTIDetectionDataset(load_prediction=NAME, load_confidence=True) takes its labels from
+                             <root>/segm_preds/NAME/<id>/segm.npy and scales every object's one-hot column by conf.npy beside it
 
 Predicted segmentations (`_save_predsegm`, written by test_seg.py under <root>/segm_preds/<name>): int64 labels per frame as
-<id>/segm{1,2}.npy (KITTI-SF), <id>/segm_%02d.npy (OGC-DR; SAPIEN with <id> = %06d), <id>/segm.npy (KITTI-Det, SemanticKITTI).
+<id>/segm{1,2}.npy (KITTI-SF), <id>/segm_%02d.npy (OGC-DR; SAPIEN with <id> = %06d), <id>/segm.npy (KITTI-Det, SemanticKITTI;
+with `conf=`, export_pseudo_labels.py, also <id>/conf.npy: one float32 confidence per distinct label, in ascending label order).
 
 A sample is (pcs (t, N, 3) f32, segms (t, N) i32, flows (t, N, 3) f32, valids (t, N) f32), t = 2 frames, or 4 with
 `aug_transform` (two random similarity transforms of the pair, utils/data_util.py:140-195).  With `onehot_label=True` — what the
@@ -44,7 +47,7 @@ import numpy as np
 from torch.utils.data import Dataset
 
 from .utils import flow_store
-from .utils.data_util import augment_transform, batch_segm_to_mask, compress_label_id
+from .utils.data_util import augment_transform, batch_segm_to_mask, batch_segm_to_mask_withconf, compress_label_id
 
 
 def _one_hot(segms, max_n_object, ignore_npoint_thresh):
@@ -476,8 +479,11 @@ class SapienDataset(Dataset):
 class _SingleFrameDataset(Dataset):
     """The sample contract of the two single-frame sets (dataset_kittidet.py:73-114, dataset_semantickitti.py:53-85): centring
     on the frame's own mean, labels compressed per frame, the frame duplicated to two views, zero flows, valids of ones.
-    `onehot_label` (KITTI-Det): one-hot masks and the valids of batch_segm_to_mask instead (dataset_kittidet.py:95-112)."""
+    `onehot_label` (KITTI-Det): one-hot masks and the valids of batch_segm_to_mask instead (dataset_kittidet.py:95-112).
+    `predsegm_path` (KITTI-Det): the labels come from <predsegm_path>/<id>/segm.npy instead of the ground truth, and under
+    `onehot_label` every object's column is scaled by its confidence (dataset_kittidet.py:63-70, :77-79, :92-101)."""
     onehot_label, max_n_object, ignore_npoint_thresh = False, 18, 0
+    predsegm_path, load_confidence = None, False
 
     def __len__(self):
         return len(self.data_ids)
@@ -486,14 +492,29 @@ class _SingleFrameDataset(Dataset):
         d = os.path.join(self.data_root, self.data_ids[idx])
         return np.load(os.path.join(d, "pc.npy")), np.load(os.path.join(d, "segm.npy"))
 
+    def _load_predsegm(self, idx):
+        """-> (labels, confidences) of a saved prediction; ones(max_n_object) without `load_confidence`."""
+        d = os.path.join(self.predsegm_path, self.data_ids[idx])
+        segm = np.load(os.path.join(d, "segm.npy"))
+        if self.load_confidence:
+            conf = np.load(os.path.join(d, "conf.npy")).astype(np.float32)
+        else:
+            conf = np.ones((self.max_n_object), dtype=np.float32)
+        return segm, conf
+
     def __getitem__(self, sid):
         pc, segm = self._load_data(sid)
+        if self.predsegm_path is not None:
+            segm, conf = self._load_predsegm(sid)
         if self.decentralize:
             pc = pc - pc.mean(0)
         segm = compress_label_id(segm)
         pcs, segms = np.stack([pc, pc], 0), np.stack([segm, segm], 0)
         flows = np.zeros_like(pcs)
-        if self.onehot_label:
+        if self.onehot_label and self.predsegm_path is not None:
+            assert self.max_n_object > 0, 'max_n_object must be above 0!'
+            segms, valids = batch_segm_to_mask_withconf(segms, [conf, conf], self.max_n_object, self.ignore_npoint_thresh)
+        elif self.onehot_label:
             segms, valids = _one_hot(segms, self.max_n_object, self.ignore_npoint_thresh)
         else:
             valids = np.ones_like(segms, dtype=np.float32)
@@ -504,20 +525,26 @@ class _SingleFrameDataset(Dataset):
         return (pcs.astype(np.float32), segms.astype(np.float32 if self.onehot_label else np.int32), flows.astype(np.float32),
                 valids.astype(np.float32))
 
-    def _save_predsegm(self, mask_or_hard, save_root, batch_size, n_frame=1, offset=0):
+    def _save_predsegm(self, mask_or_hard, save_root, batch_size, n_frame=1, offset=0, conf=None):
         """(B, N, K) masks or (B, N) hard labels -> <save_root>/<id>/segm.npy, int64; sample `offset * batch_size + i`, whatever
-        n_frame (dataset_kittidet.py:117-129)."""
+        n_frame (dataset_kittidet.py:117-129).  `conf`: one array of confidences per sample (metrics/seg_conf.py), written as
+        float32 to <save_root>/<id>/conf.npy beside it — the file `load_confidence` reads; the reference has no writer of it."""
         _save_frame_labels(mask_or_hard, save_root, batch_size, 1, offset, lambda idx: self.data_ids[idx],
                            lambda k: "segm.npy")
+        for i, c in enumerate(conf if conf is not None else ()):
+            np.save(os.path.join(save_root, self.data_ids[offset * batch_size + i], "conf.npy"), np.asarray(c, dtype=np.float32))
 
 
 class KITTIDetectionDataset(_SingleFrameDataset):
-    """Reference: datasets/dataset_kittidet.py:9-129.  `load_prediction` / `load_confidence` (training on the predicted
-    segmentations of another model, with batch_segm_to_mask_withconf) stay out: no driver of this package uses them."""
+    """Reference: datasets/dataset_kittidet.py:9-129.  `load_prediction`: train on the segmentations another model saved under
+    <data_root>/segm_preds/<load_prediction> (test_seg.py --save) instead of the ground truth; `load_confidence`: scale every
+    object's target column by the confidence in conf.npy beside them (export_pseudo_labels.py), ones otherwise."""
 
     def __init__(self, data_root, mapping_path, decentralize=False, aug_transform=False, aug_transform_args=None,
-                 onehot_label=False, max_n_object=18, ignore_npoint_thresh=0):
+                 onehot_label=False, max_n_object=18, ignore_npoint_thresh=0, load_prediction=None, load_confidence=False):
         self.onehot_label, self.max_n_object, self.ignore_npoint_thresh = onehot_label, max_n_object, ignore_npoint_thresh
+        self.predsegm_path = None if load_prediction is None else os.path.join(data_root, "segm_preds", load_prediction)
+        self.load_confidence = load_confidence
         self.data_root = os.path.join(data_root, "downsampled")
         with open(mapping_path, "r") as f:
             self.data_ids = f.read().strip().split("\n")

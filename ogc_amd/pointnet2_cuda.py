@@ -407,6 +407,14 @@ def flow_eval_wrapper(b, n, gt_flow, flow_pred, epe_norm_thresh, eps, epe_sum, c
          _check(epe_sum, torch.float64, "epe_sum"), _i(counts, "counts"))
 
 
+def slot_confidence_wrapper(b, n, k, mask, hard, slots, sizes, conf, n_object):
+    """Confidences of b predicted segmentations in one launch (ogc_slot_confidence): mask (b, n, k) f32 -> hard (b, n) i32 the
+    arg-max labels (None: not written), slots / sizes (b, k) i32 and conf (b, k) f32 of the slots that own a point, in ascending
+    slot index (-1 / 0 / 0 behind them), n_object (b,) i32."""
+    _run("ogc_slot_confidence", mask, b, n, k, _f(mask, "mask"), _opt(hard, torch.int32, "hard"), _i(slots, "slots"),
+         _i(sizes, "sizes"), _f(conf, "conf"), _i(n_object, "n_object"))
+
+
 SCAN_CROP_TILE = 1024        # OGC_SCAN_CROP_TILE: points per workgroup of the crop kernels
 SCAN_CROP_CAMERA_DOUBLES = 36  # OGC_SCAN_CROP_CAMERA_DOUBLES: V2C (12) | R0 (9) | P (12) | width | height | R0 applied
 BOX_SEGM_CHUNK = 128         # OGC_BOX_SEGM_CHUNK: boxes staged in LDS at a time

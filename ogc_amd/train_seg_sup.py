@@ -18,6 +18,12 @@ iteration and epoch come from metrics.seg_eval — one ogc_seg_eval launch and o
 full soft masks to the host every iteration.  `_train_it` therefore returns device tensors.  No tensorboard: one JSON line per
 epoch.  The Waymo baseline (train_seg_waymo_sup.py) is ogc_amd/train_seg_waymo_sup.py, a subclass of this Trainer on batches
 without flows.  Out of scope: data-parallel training, HIP-graph replay.
+
+Self-training (kittidet): `data.load_prediction: NAME` makes the TRAIN set read its labels from <root>/segm_preds/NAME, where
+`export_pseudo_labels --split train` (or `test_seg --split train --save`) left them, and `data.load_confidence: true` scales
+every object's target column by the confidence `export_pseudo_labels` wrote beside them (datasets.py, the reference's reader
+arguments).  The validation set keeps its ground truth.  The reference's trainer never passes these two arguments to its reader:
+the config keys are this package's own.
 """
 import argparse
 import json
@@ -213,6 +219,9 @@ def build_sets(cfg, roots):
                                                       view_sels=KITTISF_VIEW_SELS, decentralize=decentralize, onehot_label=True,
                                                       max_n_object=n_slot, ignore_npoint_thresh=thresh, **extra))
         elif name == "kittidet":
+            if split == "train":   # the predictions of another model as labels; validation stays on the ground truth
+                extra = dict(extra, load_prediction=data.get("load_prediction"),
+                             load_confidence=bool(data.get("load_confidence", False)))
             out.append(datasets.KITTIDetectionDataset(data_root=root, mapping_path=mapping, decentralize=decentralize,
                                                       onehot_label=True, max_n_object=n_slot, ignore_npoint_thresh=thresh, **extra))
         else:
