@@ -110,6 +110,10 @@ def _adam_kernel_step(optimizer, tables_only=False):
         L = _lib.load()
         if not params or len(params) > L.ogc_adam_max_tensors():
             return None
+        if any(p.numel() == 0 for p in params):
+            # no chunk row would carry its step count (torch advances it), and its gradient's data_ptr() is null, which
+            # ogc_adam_step refuses
+            return None
         states = [optimizer.state.get(p) for p in params]
         if any(not st or "exp_avg" not in st or not torch.is_tensor(st.get("step")) for st in states):
             return None  # first step: torch builds the state
