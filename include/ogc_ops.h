@@ -56,7 +56,7 @@ enum {
  * _chunk likewise.  ogc_kittisf_unproject and ogc_png_unfilter likewise.  ogc_live_steps_fwd, ogc_conv1x1_gemm_affine_first_live
  * and ogc_conv1x1_gemm_affine_pool_live likewise.  ogc_moving_stats / _label_cap likewise.  ogc_surface_candidates, ogc_surface_thin /
  * _ws_bytes and ogc_nearest_label likewise.  ogc_depth_render / _ws_bytes / _timed and ogc_depth_points likewise.
- * ogc_slot_confidence likewise. */
+ * ogc_slot_confidence likewise.  ogc_room_compose and ogc_mesh_apply_poses likewise. */
 #define OGC_VERSION 208
 int ogc_version(void);
 /* 0: the squared distance of every search is the reference's SOURCE expression, ((dx*dx) + (dy*dy)) + (dz*dz), one rounding per
@@ -771,6 +771,66 @@ int ogc_depth_points(int width, int height, const double *view, const double *de
  * records, item offsets, the empty image; the depth pass; the face pass}.  Same results, same refusals. */
 int ogc_depth_render_timed(int V, int F, const double *vertices, const int *faces, const double *view, int width, int height,
                            double *depth, int *face, int *status, void *ws, long long ws_bytes, float *stage_ms, ogc_stream_t stream);
+
+/* Scene composition of the OGC-DR preparation (csrc/room_compose.hip): where the objects of a room stand in every frame,
+ * what data_prepare/ogcdr/build_ogcdr.py:130-320 and :438-470 draw from np.random.  The definition below is THIS package's contract;
+ * the reference's random stream cannot be reproduced.  All arithmetic is fp64, one rounding per operation, nothing contracted;
+ * tests/ogcdr_compose_cases.py repeats it in numpy with sequential attempt loops.
+ *
+ * ogc_room_compose composes T trial scenes, one workgroup each.  Device memory: vertices (V, 3) f64, the canonical meshes of all
+ * objects of all trials concatenated; vert_offsets (O + 1) i32; obj_offsets (T + 1) i32, the objects of trial t; room (T, 2) f64, the
+ * xz range; seeds (T) i64.  HOST memory, read before the call returns: constants, OGC_ROOM_DOUBLES doubles = {ground_level,
+ * wall_thickness, y angle range lo, hi, motion angle range about y lo, hi, about x or z lo, hi, prob_rotation_y, shift range lo, hi},
+ * all finite (the reference: -0.49, 0.01, 0, 360, -10, 10, -10, 10, 0.6, 0.02, 0.04; its prob_rotation is 1 and no parameter), and
+ * limits, OGC_ROOM_INTS ints = {n_frame in [1, 8], max_iter in [1, 65536], max_retry in [0, 255]}.
+ *   random     Philox4x32-10 as in ogc_surface_candidates, key = (seed & 0xffffffff, seed >> 32) of the trial's seed, counter =
+ *              (attempt, object, frame * 256 + fails, stream); object is the index inside the trial, fails the trial's running count of
+ *              failed frame tries when the frame is tried (0 for frame 0).  Words (0, 1) and words (2, 3) give one uniform each.
+ *              stream 0: attempt 0 gives u_a, u_b, attempt 1 gives u_c (first uniform).  stream 1: the two placement uniforms of
+ *              attempt i (x, then z).  stream 2: the two sign uniforms of attempt i.  A range [lo, hi] is drawn as lo + u * (hi - lo).
+ *   sin, cos   of an angle a in degrees, by this sequence, so that no libm decides a bit: q = rint(a / 90); r = a - 90 * q;
+ *              t = r * K, K = 0x1.1df46a2529d39p-6, the double nearest pi / 180; s = t * t; ps and pc the Horner evaluations, innermost
+ *              first, of the coefficients (-1)^k / (2k + 1)! and (-1)^k / (2k)!, k = 1 .. 8, each rounded to double (ps = c1 + s * (c2 +
+ *              s * (... + s * c8))); sin_t = t + t * (s * ps); cos_t = 1 + s * pc; q mod 4 = 0, 1, 2, 3 picks (sin, cos) = (sin_t, cos_t),
+ *              (cos_t, -sin_t), (-sin_t, -cos_t), (-cos_t, sin_t).  Within 2^-52 of the true values (tests/test_ogcdr_compose_cpu.py).
+ *   rotation   frame 0: about y by the y angle range at u_a.  Frame f >= 1: if u_a < prob_rotation_y about y by the first motion range
+ *              at u_b, otherwise by the second motion range at u_b about x if u_c < 0.5, about z otherwise.  The matrices are scipy's
+ *              Rotation.from_euler on one lower-case axis: x [1 0 0; 0 c -s; 0 s c], y [c 0 s; 0 1 0; -s 0 c], z [c -s 0; s c 0; 0 0 1].
+ *              R_f = r R_(f-1), every entry ((r_i0 * R_0j + r_i1 * R_1j) + r_i2 * R_2j).
+ *   box        of an object under R: per axis i the minimum and maximum over its vertices of ((R_i0 * x + R_i1 * y) + R_i2 * z), then
+ *              + 0.0, so that a zero extreme is +0 whichever vertex gave it.  t_y = ground_level - min_y.
+ *   meet       two xz boxes [lo, hi] meet iff in both axes |c1 - c2| < (w1 + w2) / 2, c = (lo + hi) / 2, w = hi - lo of the stored
+ *              corners (check_intersection_interval).
+ *   frame 0    objects in index order.  b = max - min in x and z; attempt i: loc0 = (-room / 2 + wall) + u * ((room - b) - 2 * wall) per
+ *              axis, the box [loc0, loc0 + b]; the lowest attempt below max_iter whose box meets no earlier object's box of this frame
+ *              is accepted: t_xz = loc0 - min_xz.  An object without one: code 1.
+ *   frame f    lo = min_xz + t_xz of the last frame, hi = max_xz + that, b = hi - lo; attempt i: d = +-(shift lo + u * (hi - lo)) per
+ *              axis, + iff the sign uniform < 0.5; loc0 = lo + d; rejected if in either axis loc0 < -room / 2 + wall or
+ *              loc0 > (room / 2 - wall) - b, otherwise tested as in frame 0 with the box [loc0, loc0 + b]; t_xz = t_xz of the last
+ *              frame + d.  An object without an accepted attempt fails the try: fails + 1 > max_retry gives code 2, otherwise
+ *              fails += 1 and the frame is drawn again from its rotations.
+ * Out: poses (O, n_frame, 4, 4) f64, [R t; 0 0 0 1], the map from the canonical mesh to the frame's mesh; attempt (O, n_frame) i32, the
+ * accepted attempt; fails (T, n_frame) i32, the failure count at which each frame was accepted; status (T, 2) i32 = {code, frame}:
+ * 0 composed; 1 frame 0 found no place for an object; 2 the dynamics used up its retries at `frame`; 3 a vertex or room value of the
+ * trial that is not finite; 4, in every trial, offsets that do not start at 0, descend, do not end at V / O, delimit an object without
+ * vertices or give a trial more than OGC_ROOM_MAX_OBJECTS objects (the offsets are device memory: this limit is found there).  With a
+ * non-zero code the trial's other outputs are unspecified.  T == 0: OGC_OK.  Negative sizes, 3 V or 2 T beyond 32 bits, a constant
+ * that is not finite, a limit outside its range, a null pointer: OGC_ERR_INVALID_ARG, nothing launched.
+ * ogc_mesh_apply_poses: vertices (V, 3) f64, vert_offsets (O + 1) i32 (ascending from 0 to V: not checked, a vertex takes the pose of
+ * the last object whose offset does not exceed it), poses (O, n_frame, 4, 4) f64 -> out (n_frame, V, 3) f64,
+ * out_i = ((R_i0 * x + R_i1 * y) + R_i2 * z) + t_i, one thread per vertex and frame.  V == 0 or n_frame == 0: OGC_OK.  Negative sizes,
+ * 3 V n_frame beyond 32 bits, vertices without an object, a null pointer: OGC_ERR_INVALID_ARG. */
+#define OGC_ROOM_DOUBLES 11
+#define OGC_ROOM_INTS 3
+#define OGC_ROOM_MAX_OBJECTS 32
+#define OGC_ROOM_MAX_FRAMES 8
+#define OGC_ROOM_MAX_ITER 65536
+#define OGC_ROOM_MAX_RETRY 255
+int ogc_room_compose(int T, int O, int V, const double *vertices, const int *vert_offsets, const int *obj_offsets, const double *room,
+                     const long long *seeds, const double *constants, const int *limits, double *poses, int *attempt, int *fails,
+                     int *status, ogc_stream_t stream);
+int ogc_mesh_apply_poses(int V, int O, int n_frame, const double *vertices, const int *vert_offsets, const double *poses, double *out,
+                         ogc_stream_t stream);
 
 /* Attention core of the MaskFormer head's nn.MultiheadAttention layers
  *   utils/transformer_util.py:5-62 (cross-attention slots <- points, self-attention among the slots; 8 heads,

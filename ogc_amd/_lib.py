@@ -101,6 +101,8 @@ SIGNATURES = {
     "ogc_depth_render": [_int, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _ll, _vp],
     "ogc_depth_render_timed": [_int, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _ll, _vp, _vp],
     "ogc_depth_points": [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_room_compose": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ogc_mesh_apply_poses": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_concat": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_fwd": [_int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ogc_group_linear_bwd": [_int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -31,6 +31,17 @@ void *ogc_workspace(hipStream_t stream, size_t bytes);
 
 static inline int ogc_divup(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// the segment that owns item i of a ragged array: the last m with offsets[m] <= i (offsets ascending, offsets[0] == 0, i < offsets[M]).
+// Whatever the offsets hold, only offsets[1 .. M - 1] are read and the result lies in [0, M - 1].
+__device__ __forceinline__ int ogc_owner(const int *__restrict__ offsets, int M, int i) {
+    int lo = 0, hi = M; // invariant: offsets[lo] <= i < offsets[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // ---- the deterministic-gradient mode (det.hip; ogc_set_deterministic) -------------------------------------------------------
 bool ogc_deterministic();
 void *ogc_det_scratch(hipStream_t stream, size_t bytes); // grow-only scratch per (device, stream), apart from ogc_workspace

@@ -16,42 +16,12 @@
 #include <math.h>
 
 #include "ogc_common.h"
+#include "philox.h"
 
 namespace {
 
 constexpr int SC_THREADS = 256;
 constexpr int SC_CHECK_THREADS = 1024;
-
-struct Philox4 {
-    uint32_t w[4];
-};
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
-
-__device__ __forceinline__ double uniform53(uint32_t hi, uint32_t lo) {
-    return (double)(((uint64_t)(hi >> 5) << 26) | (uint64_t)(lo >> 6)) * 0x1.0p-53; // exact: a 53-bit integer, a power of two
-}
-
-// the mesh that owns item i: the last m with offsets[m] <= i (offsets ascending, offsets[0] == 0, i < offsets[M])
-__device__ __forceinline__ int owner(const int *__restrict__ offsets, int M, int i) {
-    int lo = 0, hi = M; // invariant: offsets[lo] <= i < offsets[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(SC_CHECK_THREADS) void surface_check_kernel(int C, int M, int V, int F, const int *__restrict__ faces,
                                                                          const double *__restrict__ cum_area,
@@ -91,7 +61,7 @@ __global__ __launch_bounds__(SC_THREADS) void surface_candidates_kernel(int C, i
     if (status[0] != 0) return;
     const int i = blockIdx.x * SC_THREADS + threadIdx.x;
     if (i >= C) return;
-    const int m = owner(cand_offsets, M, i);
+    const int m = ogc_owner(cand_offsets, M, i);
     const uint32_t j = (uint32_t)(i - cand_offsets[m]);
     const Philox4 a = philox4x32_10(j, (uint32_t)m, 0u, 0u, key0, key1);
     const Philox4 b = philox4x32_10(j, (uint32_t)m, 1u, 0u, key0, key1);

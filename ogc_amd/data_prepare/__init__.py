@@ -20,12 +20,15 @@ the readers of ogc_amd/datasets.py load.
   collect_segm           python -m ogc_amd.data_prepare.collect_segm --src_root <OGC-DR root> --dest_root <OGC-DRSV root>
   build_ogcdrsv          python -m ogc_amd.data_prepare.build_ogcdrsv --src_root <OGC-DR root> --dest_root <OGC-DRSV root>
                          (mesh_ops.default_view / depth_render / render_points over csrc/depth_render.hip)
+  build_ogcdr            python -m ogc_amd.data_prepare.build_ogcdr <data_root> --split_root <raw_splits> [--keep_background]
+                         (mesh_ops.compose_rooms / apply_poses over csrc/room_compose.hip)
 
 A frame is one upload, crop -> FPS -> labels on the device, one download.  There is no CPU path.
 """
 
 _EXPORTS = {"surface_candidates": "mesh_ops", "surface_thin": "mesh_ops", "nearest_label": "mesh_ops", "sample_surface_even": "mesh_ops",
             "default_view": "mesh_ops", "depth_render": "mesh_ops", "render_points": "mesh_ops",
+            "compose_rooms": "mesh_ops", "apply_poses": "mesh_ops",
             "read_obj": "mesh_io", "write_obj": "mesh_io", "read_pcd": "mesh_io", "write_pcd": "mesh_io"}
 __all__ = sorted(_EXPORTS)
 

@@ -3,7 +3,7 @@ DESIGN §4m): random points on mesh surfaces, their thinning to an even sampling
 Inputs are CUDA tensors and results stay on the device; the host reads a status word per call (and, in sample_surface_even, the
 areas it needs for the radii, which it computes itself).  There is no CPU path.
 The depth render of the OGC-DRSV preparation (csrc/depth_render.hip) is here too: default_view, depth_render and
-render_points."""
+render_points.  So is the scene composition of build_ogcdr (csrc/room_compose.hip): compose_rooms and apply_poses."""
 import collections
 import math
 
@@ -268,6 +268,76 @@ def render_points(vertices, faces, view, width, height, face_offsets=None):
         return points, pixel, face_out
     mesh_idx = (torch.searchsorted(face_offsets, face_out, right=True) - 1).to(torch.int32)
     return points, pixel, face_out, mesh_idx
+
+
+COMPOSE_STATUS = {3: "a vertex or room value that is not finite",
+                  4: "offsets that do not start at 0, descend, do not end at the array sizes, delimit an object without vertices or give "
+                     "a trial more than 32 objects"}
+# the constants of ogc_room_compose in the order the library takes them, with the reference's values (build_ogcdr.py:51-67)
+COMPOSE_DOUBLES = collections.OrderedDict((("ground_level", -0.5 + 0.01), ("wall_thickness", 0.01), ("y_angle_lo", 0.0), ("y_angle_hi", 360.0),
+                                           ("mot_y_angle_lo", -10.0), ("mot_y_angle_hi", 10.0), ("mot_xz_angle_lo", -10.0),
+                                           ("mot_xz_angle_hi", 10.0), ("prob_rotation_y", 0.6), ("mot_transl_lo", 0.02),
+                                           ("mot_transl_hi", 0.04)))
+COMPOSE_INTS = collections.OrderedDict((("n_frame", 4), ("max_iter", 1000), ("max_retry", 20)))
+Composition = collections.namedtuple("Composition", "poses attempt fails status")
+
+
+def compose_rooms(vertices, vert_offsets, obj_offsets, room, seeds, **constants):
+    """T trial scenes composed in one launch (include/ogc_ops.h: ogc_room_compose): vertices (V, 3) fp64, the canonical meshes of all
+    objects of all trials concatenated, vert_offsets (O + 1,) int32, obj_offsets (T + 1,) int32, room (T, 2) fp64 and seeds (T,)
+    int64, CUDA tensors; the constants by keyword, any of COMPOSE_DOUBLES and COMPOSE_INTS, the reference's values otherwise
+    -> Composition(poses (O, n_frame, 4, 4) fp64, attempt (O, n_frame) int32, fails (T, n_frame) int32, status (T, 2) int32) on the
+    device.  status[t] = {code, frame}: 0 composed, 1 frame 0 found no place, 2 the dynamics used up its retries; these are results
+    and the caller reads them with the poses.  One host read here: whether any code is 3 or 4, which raise."""
+    unknown = set(constants) - set(COMPOSE_DOUBLES) - set(COMPOSE_INTS)
+    if unknown:
+        raise TypeError("compose_rooms: unknown constants %s" % sorted(unknown))
+    tensors = ((vertices, "vertices", torch.float64), (vert_offsets, "vert_offsets", torch.int32), (obj_offsets, "obj_offsets", torch.int32),
+               (room, "room", torch.float64), (seeds, "seeds", torch.int64))
+    _check_tensors(tensors)
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be (V, 3), got %s" % (tuple(vertices.shape),))
+    if vert_offsets.dim() != 1 or vert_offsets.shape[0] < 1 or obj_offsets.dim() != 1 or obj_offsets.shape[0] < 1:
+        raise ValueError("vert_offsets must be (O + 1,) and obj_offsets (T + 1,), got %s and %s"
+                         % (tuple(vert_offsets.shape), tuple(obj_offsets.shape)))
+    n_object, n_trial = vert_offsets.shape[0] - 1, obj_offsets.shape[0] - 1
+    if tuple(room.shape) != (n_trial, 2) or tuple(seeds.shape) != (n_trial,):
+        raise ValueError("room must be (%d, 2) and seeds (%d,), got %s and %s" % (n_trial, n_trial, tuple(room.shape), tuple(seeds.shape)))
+    _check_contiguous(tensors)
+    doubles = [float(constants.get(k, v)) for k, v in COMPOSE_DOUBLES.items()]
+    n_frame, max_iter, max_retry = (int(constants.get(k, v)) for k, v in COMPOSE_INTS.items())
+    dev = vertices.device
+    # n_frame sizes the outputs: its range is asked for here as well as by the library, so that nothing absurd is allocated
+    frames = n_frame if 1 <= n_frame <= 8 else 1
+    out = Composition(torch.empty(n_object, frames, 4, 4, dtype=torch.float64, device=dev),
+                      torch.empty(n_object, frames, dtype=torch.int32, device=dev),
+                      torch.empty(n_trial, frames, dtype=torch.int32, device=dev), torch.empty(n_trial, 2, dtype=torch.int32, device=dev))
+    _native.room_compose_wrapper(n_trial, n_object, vertices.shape[0], vertices, vert_offsets, obj_offsets, room, seeds, doubles,
+                                 (n_frame, max_iter, max_retry), out.poses, out.attempt, out.fails, out.status)
+    if n_trial:
+        code = int(out.status[:, 0].max().item())
+        if code >= 3:
+            raise ValueError("compose_rooms: " + COMPOSE_STATUS.get(code, "status %d" % code))
+    return out
+
+
+def apply_poses(vertices, vert_offsets, poses):
+    """Every object's vertices under its pose of every frame (ogc_mesh_apply_poses): vertices (V, 3) fp64, vert_offsets (O + 1,) int32
+    ascending from 0 to V, poses (O, n_frame, 4, 4) fp64, CUDA tensors -> (n_frame, V, 3) fp64 on the device,
+    ((R_i0 * x + R_i1 * y) + R_i2 * z) + t_i.  No host read."""
+    tensors = ((vertices, "vertices", torch.float64), (vert_offsets, "vert_offsets", torch.int32), (poses, "poses", torch.float64))
+    _check_tensors(tensors)
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be (V, 3), got %s" % (tuple(vertices.shape),))
+    if vert_offsets.dim() != 1 or vert_offsets.shape[0] < 1:
+        raise ValueError("vert_offsets must be (O + 1,), got %s" % (tuple(vert_offsets.shape),))
+    n_object = vert_offsets.shape[0] - 1
+    if poses.dim() != 4 or poses.shape[0] != n_object or tuple(poses.shape[2:]) != (4, 4):
+        raise ValueError("poses must be (%d, n_frame, 4, 4), got %s" % (n_object, tuple(poses.shape)))
+    _check_contiguous(tensors)
+    out = torch.empty(poses.shape[1], vertices.shape[0], 3, dtype=torch.float64, device=vertices.device)
+    _native.mesh_apply_poses_wrapper(vertices.shape[0], n_object, poses.shape[1], vertices, vert_offsets, poses, out)
+    return out
 
 
 def even_radius(area, count):

@@ -548,6 +548,30 @@ def depth_points_wrapper(width, height, view, depth, face, points, pixel, face_o
          _i(pixel, "pixel"), _i(face_out, "face_out"), _i(status, "status"))
 
 
+ROOM_DOUBLES, ROOM_INTS = 11, 3     # OGC_ROOM_DOUBLES, OGC_ROOM_INTS
+ROOM_MAX_OBJECTS = 32               # OGC_ROOM_MAX_OBJECTS
+
+
+def room_compose_wrapper(t, o, v, vertices, vert_offsets, obj_offsets, room, seeds, constants, limits, poses, attempt, fails, status):
+    """t trial scenes composed in one launch (ogc_room_compose): vertices (v, 3) f64, vert_offsets (o + 1,) and obj_offsets (t + 1,)
+    i32, room (t, 2) f64, seeds (t,) i64, constants 11 host doubles, limits 3 host ints = (n_frame, max_iter, max_retry)
+    -> poses (o, n_frame, 4, 4) f64, attempt (o, n_frame) i32, fails (t, n_frame) i32, status (t, 2) i32 = {code, frame}."""
+    import ctypes
+    dbl, ints = [float(x) for x in constants], [int(x) for x in limits]
+    if len(dbl) != ROOM_DOUBLES or len(ints) != ROOM_INTS:
+        raise ValueError("the constants are %d doubles and %d ints, got %d and %d" % (ROOM_DOUBLES, ROOM_INTS, len(dbl), len(ints)))
+    _run("ogc_room_compose", status, int(t), int(o), int(v), _d(vertices, "vertices"), _i(vert_offsets, "vert_offsets"),
+         _i(obj_offsets, "obj_offsets"), _d(room, "room"), _check(seeds, torch.int64, "seeds"), (ctypes.c_double * ROOM_DOUBLES)(*dbl),
+         (ctypes.c_int * ROOM_INTS)(*ints), _d(poses, "poses"), _i(attempt, "attempt"), _i(fails, "fails"), _i(status, "status"))
+
+
+def mesh_apply_poses_wrapper(v, o, n_frame, vertices, vert_offsets, poses, out):
+    """Every object's vertices under its pose of every frame (ogc_mesh_apply_poses): vertices (v, 3) f64, vert_offsets (o + 1,) i32,
+    poses (o, n_frame, 4, 4) f64 -> out (n_frame, v, 3) f64."""
+    _run("ogc_mesh_apply_poses", out, int(v), int(o), int(n_frame), _d(vertices, "vertices"), _i(vert_offsets, "vert_offsets"),
+         _d(poses, "poses"), _d(out, "out"))
+
+
 def png_unfilter(stream_bytes, height, row_bytes, bpp):
     """The row filters of an inflated PNG stream undone on the host (ogc_png_unfilter; nothing is launched): bytes of
     height * (1 + row_bytes) -> numpy uint8 (height, row_bytes)."""

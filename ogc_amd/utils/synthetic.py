@@ -907,6 +907,46 @@ def box_mesh_between(lo, hi):
     return vertices + (lo + hi) / 2, faces
 
 
+def ogcdr_background_meshes(xz_range, wall_height):
+    """Ground and the four walls of a room as get_ground / get_walls lay them out around `xz_range` (build_ogcdr.py:370-405)
+    -> ((vertices, faces) of the ground, [(vertices, faces)] of wall 0 .. 3)."""
+    xr = xz_range
+    gl, wt = OGCDR_GROUND_LEVEL, OGCDR_WALL_THICKNESS
+    ground = box_mesh_between([-xr[0] / 2, OGCDR_GROUND_HEIGHT, -xr[1] / 2], [xr[0] / 2, gl, xr[1] / 2])
+    walls = (([-xr[0] / 2, gl, -xr[1] / 2], [xr[0] / 2, gl + wall_height, -xr[1] / 2 + wt]),
+             ([-xr[0] / 2, gl, -xr[1] / 2], [-xr[0] / 2 + wt, gl + wall_height, xr[1] / 2]),
+             ([-xr[0] / 2, gl, xr[1] / 2 - wt], [xr[0] / 2, gl + wall_height, xr[1] / 2]),
+             ([xr[0] / 2 - wt, gl, -xr[1] / 2], [xr[0] / 2, gl + wall_height, xr[1] / 2]))
+    return ground, [box_mesh_between(lo, hi) for lo, hi in walls]
+
+
+def write_shapenet_root(data_root, split_root, n_models, classes=("02828884", "03001627", "04379243"), seed=9700):
+    """A small root in the layout build_ogcdr reads: <data_root>/ShapeNet_mesh/<class>/<model>/model.obj, `n_models` models of
+    ogcdr_object_mesh per class and split, away from the origin and of differing sizes so that scaling and centring have work to
+    do, and <split_root>/<class>/{train,val,test}.lst naming them.  Returns {class: {split: [model]}}."""
+    import os
+
+    import numpy as np
+
+    from ..data_prepare.mesh_io import write_obj
+    rs = np.random.RandomState(seed)
+    out = {}
+    for c, cl in enumerate(classes):
+        os.makedirs(os.path.join(split_root, cl), exist_ok=True)
+        out[cl] = {}
+        for s, split in enumerate(("train", "val", "test")):
+            models = ["%s%04d" % (split, m) for m in range(n_models)]
+            for m, model in enumerate(models):
+                vertices, faces = ogcdr_object_mesh(c + s + m, rs)
+                os.makedirs(os.path.join(data_root, "ShapeNet_mesh", cl, model), exist_ok=True)
+                write_obj(os.path.join(data_root, "ShapeNet_mesh", cl, model, "model.obj"),
+                          vertices * (1.0 + 9.0 * rs.rand()) + (rs.rand(3) - 0.5), faces)
+            with open(os.path.join(split_root, cl, split + ".lst"), "w") as f:
+                f.write("\n".join(models) + "\n")
+            out[cl][split] = models
+    return out
+
+
 def write_ogcdr_mesh_root(root, n_scenes, n_objects=3, n_frames=4, seed=9500, split="val", xz_range=(0.4, 0.3), wall_height=0.08,
                           meta_key="xz_ground_range"):
     """`n_scenes` scenes in the layout build_ogcdr.py leaves and sample_pointcloud reads: <root>/mesh/<NN_id>/object_FF_OO.obj — the
@@ -932,14 +972,11 @@ def write_ogcdr_mesh_root(root, n_scenes, n_objects=3, n_frames=4, seed=9500, sp
         with open(os.path.join(mesh_dir, "meta.pkl"), "wb") as f:
             pickle.dump({"room_id": i, "split": split, "n_object": n_objects, meta_key: xr.copy(), "wall_height": float(wall_height)}, f,
                         protocol=pickle.HIGHEST_PROTOCOL)
-        gl, wt = OGCDR_GROUND_LEVEL, OGCDR_WALL_THICKNESS
-        write_obj(os.path.join(mesh_dir, "ground.obj"), *box_mesh_between([-xr[0] / 2, OGCDR_GROUND_HEIGHT, -xr[1] / 2], [xr[0] / 2, gl, xr[1] / 2]))
-        walls = (([-xr[0] / 2, gl, -xr[1] / 2], [xr[0] / 2, gl + wall_height, -xr[1] / 2 + wt]),
-                 ([-xr[0] / 2, gl, -xr[1] / 2], [-xr[0] / 2 + wt, gl + wall_height, xr[1] / 2]),
-                 ([-xr[0] / 2, gl, xr[1] / 2 - wt], [xr[0] / 2, gl + wall_height, xr[1] / 2]),
-                 ([xr[0] / 2 - wt, gl, -xr[1] / 2], [xr[0] / 2, gl + wall_height, xr[1] / 2]))
-        for w, (lo, hi) in enumerate(walls):
-            write_obj(os.path.join(mesh_dir, "wall_%02d.obj" % w), *box_mesh_between(lo, hi))
+        gl = OGCDR_GROUND_LEVEL
+        ground, walls = ogcdr_background_meshes(xr, wall_height)
+        write_obj(os.path.join(mesh_dir, "ground.obj"), *ground)
+        for w, wall in enumerate(walls):
+            write_obj(os.path.join(mesh_dir, "wall_%02d.obj" % w), *wall)
         objects = [ogcdr_object_mesh(k, rs) for k in range(n_objects)]
         yaw = rs.rand(n_objects) * 2 * math.pi
         shift = (rs.rand(n_objects, 3) - 0.5) * np.array([xr[0] * 0.4, 0.1, xr[1] * 0.4]) + np.array([0.0, gl + 0.12, 0.0])
