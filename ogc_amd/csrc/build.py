@@ -10,8 +10,8 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["api.hip", "det.hip", "knn.hip", "ball_query.hip", "fps.hip", "gather_group.hip", "interpolate.hip", "kabsch.hip", "rigid_icp.hip", "ground_plane.hip", "seg_eval.hip", "seg_conf.hip", "flow_eval.hip", "sup_loss.hip", "small_solvers.hip", "neighbour_loss.hip", "soft_nn.hip", "soft_carry.hip", "scan_prepare.hip", "kittisf_prepare.hip", "moving_stats.hip", "surface_candidates.hip", "surface_thin.hip", "nearest_label.hip", "depth_render.hip", "room_compose.hip", "seg_loss.hip", "group_norm.hip", "batch_norm.hip", "grid.hip", "grid_ball_query.hip", "grid_knn.hip", "conv1x1.hip", "conv1x1_h.hip", "conv1x1_wgrad.hip", "attention.hip", "slot_masks.hip", "small_linear.hip", "loss_glue.hip", "mlp_chain.hip", "gn_fused_bwd.hip", "live_steps.hip", "adam.hip", "gemm_chunk.hip", "chamfer.hip", "flow_step.hip"]
-HEADERS = ["ogc_common.h", "grid.h", "grid_dev.h", "conv_stage.h", "conv1x1_shared.h", "act_io.h", "norm_dev.h", "conv1x1_epilogue.h", "first_conv.h", "live_steps.h", "wgrad_tile_body.inc", "wgrad_shared_body.inc", "moments_body.inc", "moments_walk.inc", "svd3.h", "png_unfilter.h", "philox.h", os.path.join("..", "..", "include", "ogc_ops.h")]
+SOURCES = ["api.hip", "det.hip", "knn.hip", "ball_query.hip", "fps.hip", "gather_group.hip", "group_linear.hip", "group_reverse.hip", "interpolate.hip", "kabsch.hip", "rigid_icp.hip", "ground_plane.hip", "seg_eval.hip", "seg_conf.hip", "flow_eval.hip", "sup_loss.hip", "small_solvers.hip", "neighbour_loss.hip", "soft_nn.hip", "soft_carry.hip", "scan_prepare.hip", "kittisf_prepare.hip", "moving_stats.hip", "surface_candidates.hip", "surface_thin.hip", "nearest_label.hip", "depth_render.hip", "room_compose.hip", "seg_loss.hip", "group_norm.hip", "batch_norm.hip", "grid.hip", "grid_ball_query.hip", "grid_knn.hip", "conv1x1.hip", "conv1x1_h.hip", "conv1x1_wgrad.hip", "attention.hip", "slot_masks.hip", "small_linear.hip", "loss_glue.hip", "mlp_chain.hip", "gn_fused_bwd.hip", "live_steps.hip", "adam.hip", "gemm_chunk.hip", "chamfer.hip", "flow_step.hip"]
+HEADERS = ["ogc_common.h", "grid.h", "grid_dev.h", "conv_stage.h", "conv1x1_shared.h", "act_io.h", "norm_dev.h", "conv1x1_epilogue.h", "first_conv.h", "live_steps.h", "launch_shape.h", "group_linear_store.inc", "wgrad_tile_body.inc", "wgrad_shared_body.inc", "moments_body.inc", "moments_walk.inc", "svd3.h", "png_unfilter.h", "philox.h", os.path.join("..", "..", "include", "ogc_ops.h")]
 LIB = os.path.join(HERE, "libogc_ops.so")
 # The search kernels once more with the distance expression contracted as `nvcc --fmad=true` contracts it (ogc_common.h, OGC_FMAD):
 # libogc_ops_fmad.so = those objects + all the others of libogc_ops.so.  Opt-in at load time (OGC_FMAD=1, ogc_amd/_lib.py).

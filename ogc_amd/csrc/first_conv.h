@@ -6,7 +6,7 @@
 // matrices and its adjoint input gradient (conv1x1.hip, gn_fused_bwd.hip) — therefore take x0 and W1 and rebuild the float4 of
 // y1 they would have loaded.  The value is ONE multiply followed by fused multiply-adds over the input channels ascending:
 // the order in which v_mfma_f32_16x16x4_f32 walks k, so the result equals what ogc_conv1x1_gemm_gnstats stores, bit for bit
-// (group_linear_direct_kernel of gather_group.hip relies on the same fact).
+// (group_linear_direct_kernel of group_linear.hip relies on the same fact).
 // CP: the channel count a kernel is built for (3, 6 or 8; c0 <= CP).  Channels c0 .. CP - 1 are zeros in the lane's x0 values
 // and in the staged weights: fmaf(0, 0, v) leaves v as it is.
 #pragma once

@@ -6,6 +6,7 @@
 // slab of channels (the reference re-reads idx/weight for every channel through blockIdx.y).
 // Forward evaluation order is the reference's: (w0*p0 + w1*p1) + w2*p2, no FMA contraction.
 #include "ogc_common.h"
+#include "launch_shape.h"
 
 namespace {
 
@@ -101,12 +102,6 @@ __global__ __launch_bounds__(TI_THREADS) void three_interp_bwd_lds_kernel(int c,
     }
 }
 
-int ti_ch_per_block(int b, int c, int blocks_x) {
-    int cpb = 1;
-    while (cpb < c && (long long)b * blocks_x * ((c + 2 * cpb - 1) / (2 * cpb)) >= 2048) cpb *= 2;
-    return cpb;
-}
-
 } // namespace
 
 extern "C" int ogc_three_interpolate(int b, int c, int m, int n, const float *points, const int *idx,
@@ -117,7 +112,7 @@ extern "C" int ogc_three_interpolate(int b, int c, int m, int n, const float *po
     OGC_REQUIRE((long long)b * c * n < (1ll << 31) && (long long)b * c * m < (1ll << 31),
                 "ogc_three_interpolate: tensor exceeds 32-bit indexing");
     const int bx = ogc_divup(n, TI_THREADS);
-    const int cpb = ti_ch_per_block(b, c, bx);
+    const int cpb = pick_ch_per_block(b, c, bx);
     dim3 grid(bx, ogc_divup(c, cpb), b);
     hipLaunchKernelGGL(three_interp_fwd_kernel, grid, dim3(TI_THREADS), 0, (hipStream_t)stream, c, m, n, cpb,
                        points, idx, weight, out);
@@ -136,10 +131,7 @@ extern "C" int ogc_three_interpolate_grad(int b, int c, int n, int m, const floa
         return ogc_det_scatter_add("ogc_three_interpolate_grad", b, c, m, 3ll * n, idx, grad_out, (long long)c * n, weight, 1,
                                    grad_points, 1, (hipStream_t)stream);
     if (m <= 16384 && n >= 1024) { // LDS-privatised path: CC channel images of m floats within 64 KiB
-        int cc = 4096 / m;   // 16 KiB images (one channel when m > 4096): more workgroups per CU, see group_bwd
-        if (cc < 1) cc = 1;
-        cc = cc >= 8 ? 8 : (cc >= 4 ? 4 : (cc >= 2 ? 2 : 1));
-        while (cc > 1 && cc / 2 >= c) cc /= 2;
+        const int cc = lds_image_channels(4096, m, c); // 16 KiB images (one channel when m > 4096): more workgroups per CU, see group_bwd
         const int chunks = ogc_divup(c, cc);
         int splits = 1;
         while ((long long)b * chunks * splits < 512 && n / (splits * 2) >= 2048) splits *= 2;
@@ -158,7 +150,7 @@ extern "C" int ogc_three_interpolate_grad(int b, int c, int n, int m, const floa
         return OGC_OK;
     }
     const int bx = ogc_divup(n, TI_THREADS);
-    const int cpb = ti_ch_per_block(b, c, bx);
+    const int cpb = pick_ch_per_block(b, c, bx);
     dim3 grid(bx, ogc_divup(c, cpb), b);
     hipLaunchKernelGGL(three_interp_bwd_kernel, grid, dim3(TI_THREADS), 0, (hipStream_t)stream, c, n, m, cpb,
                        grad_out, idx, weight, grad_points);

@@ -1630,7 +1630,7 @@ class _GroupedFirstLayer(Function):
                                                 w.contiguous(), y, stats)
         elif (act16 and GROUP_LINEAR_POINT_MAJOR and M % 64 == 0 and cg in (16, 32, 64) and (npoint * nsample) % 2 == 0
                 and getattr(nat, "group_linear_fwd_pt_wrapper", None) is not None):
-            # 16-bit output: P point-major, so that a position's channels are one contiguous read (csrc/gather_group.hip)
+            # 16-bit output: P point-major, so that a position's channels are one contiguous read (csrc/group_linear.hip)
             nat.group_linear_fwd_pt_wrapper(B, M, N, npoint, nsample, gn_groups, P.transpose(1, 2).contiguous(), idx, rel, wx, y, stats)
         else:
             nat.group_linear_fwd_wrapper(B, M, N, npoint, nsample, gn_groups, P, idx, rel, wx, y, stats)

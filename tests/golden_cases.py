@@ -405,7 +405,7 @@ GATE_FLIP_TENSORS = _gate_flip_tensors()   # tests/golden/gate_flip_tensors.json
 # Round 6: EMPTY.  The 68 rows of segnet_ogcdr came from ONE product: the grouped first layer of the first level applied its
 # three feature columns per point (P = W_f f, gathered) and added W_xyz rel on top — two separately rounded halves where the
 # reference's convolution (and this library's matrix kernels) run one chain over the six input channels.  That level now takes
-# ogc_group_linear_fwd_direct (one k-ascending chain per output, csrc/gather_group.hip) and every gradient row of every fixture is
+# ogc_group_linear_fwd_direct (one k-ascending chain per output, csrc/group_linear.hip) and every gradient row of every fixture is
 # inside the ordinary bound (tools/gate_flip_list.py: 0 / 0 / 0; with OGC_GROUP_LINEAR_DIRECT=0 the 68 rows come back).
 MAX_GATE_FLIP_TENSORS = {"segnet_ogcdr": 0}
 assert {k: len(v) for k, v in GATE_FLIP_TENSORS.items()} == MAX_GATE_FLIP_TENSORS, "the exception list may only shrink"
